@@ -13,8 +13,16 @@ device before timing.
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched
 by torch.distributed.run (one rank per GPU, RCCL).  Multi-GPU = weak scaling:
 each rank owns its own stream(s); the only collective is an all_gather of the
-per-stream manifest records (after the timed region).  Rank 0 prints ONE JSON
-line.
+per-stream manifest records (after the timed region, `--full` only).  Rank 0
+prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline,
+live kernel timing of the timed steps and the roofline fractions derived from
+it).  `--full` adds the legs that take runs of their own: the copy-bandwidth
+probe (`roofline.achievable_peak`), the one-file job (`one_file_job`), the CPU
+baselines (`cpu_baseline`) and the per-stream manifest; their fields are null
+without it.  `--dump-outputs DIR` writes what the last timed step computed
+(after the pipeline's flush) as DIR/<name>.npy, see dump_outputs().
 """
 from __future__ import annotations
 
@@ -294,6 +302,47 @@ def load_traffic(workload: str):
         return None
 
 
+DUMP_MAX_SAMPLES = 1 << 22   # per sample array (16 MiB as float32)
+DUMP_MAX_FRAMES = 1 << 20    # per frame / chunk array (4 MiB as float32)
+
+
+def _dump_array(t, cap: int, seed: int) -> np.ndarray:
+    """float32 host copy of the flat device tensor ``t``; above ``cap`` elements
+    a fixed sample of it: ``cap`` positions drawn (with repetition) by
+    numpy's default_rng(seed) over [0, numel), in ascending order."""
+    import torch
+    t = t.reshape(-1)
+    if t.numel() > cap:
+        idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), cap, dtype=np.int64))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(d: str, res, stage2=None, rank: int = 0) -> None:
+    """``--dump-outputs``: what the last timed pass handed its caller (the
+    engine's Result after the pipeline's flush), as float32 ``<name>.npy``
+    files in ``d`` (ranks above 0: ``<name>.rank<r>.npy``): ``y`` the output
+    samples of all streams (flat, interleaved channels), ``states`` the gate
+    state per frame, ``chunk_peaks`` the limiter's peak per chunk; the C5 chain
+    also ``y_stage2`` / ``chunk_peaks_stage2`` (the residual EQ's output).
+    Arrays above the caps are seeded samples (_dump_array), so the files stay
+    under 64 MB whatever the workload; the same arguments give the same inputs,
+    passes and sample positions in every run."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    arrays = {"y": _dump_array(res.y, DUMP_MAX_SAMPLES, 1)}
+    if res.states is not None:
+        arrays["states"] = _dump_array(res.states, DUMP_MAX_FRAMES, 2)
+    if res.chunk_peaks is not None:
+        arrays["chunk_peaks"] = _dump_array(res.chunk_peaks.view(torch.float32), DUMP_MAX_FRAMES, 3)
+    if stage2 is not None:
+        arrays["y_stage2"] = _dump_array(stage2.y, DUMP_MAX_SAMPLES, 4)
+        arrays["chunk_peaks_stage2"] = _dump_array(stage2.chunk_peaks.view(torch.float32),
+                                                   DUMP_MAX_FRAMES, 5)
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+
+
 def relaunch(n: int) -> int:
     """``--gpus N`` without a launcher: start torch.distributed.run with N
     ranks as a CHILD process (nothing here has touched the GPU) and relay its
@@ -317,8 +366,16 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: copy-bandwidth probe "
+                         "(roofline.achievable_peak), one-file job, CPU baselines, manifest")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (after the "
+                         "pipeline's flush) as DIR/<name>.npy (float32; seeded samples of "
+                         "arrays too large to keep whole)")
     ap.add_argument("--cpu-sample-s", type=int, default=3600,
-                    help="seconds of audio for the 1-core CPU baseline (0 disables the baseline)")
+                    help="--full: seconds of audio for the 1-core CPU baseline (0 disables the "
+                         "baseline)")
     ap.add_argument("--input-gain", type=float, default=1.0,
                     help="scale the synthetic input (e.g. 0.05: no limiter chunk engages; "
                          "PMC traffic runs)")
@@ -333,7 +390,7 @@ def main():
                     help="distinct synthetic inputs of the workload's shape, used in turn by the "
                          "passes (a pipeline of different files, not one file re-processed)")
     ap.add_argument("--single-steps", type=int, default=10,
-                    help="also time this many unpipelined passes (a job of ONE file: the limiter "
+                    help="--full: also time this many unpipelined passes (a job of ONE file: the limiter "
                          "ends the pass) with their own pipeline; 0 disables")
     ap.add_argument("--dev", action="append", default=[], metavar="NAME=VALUE",
                     help="development override (TOMATIS_DEV_<NAME>, A/B experiments); "
@@ -383,6 +440,8 @@ def main():
     if (a.inputs + 3) * set_bytes > budget:
         a.single_steps = 0
     a.inputs = int(max(1, min(a.inputs, budget // set_bytes - (3 if a.single_steps else 2))))
+    if not a.full:  # (after the budget: a plain run times the inputs a --full run times)
+        a.single_steps = 0
     inputs = [ss.x]
     if mode != "timeshard":
         for j in range(1, max(1, a.inputs)):
@@ -439,11 +498,13 @@ def main():
              if k % every == min(1, every - 1) else None for k in range(a.steps)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None             # (the chain's stage-2 Result of the last pass, for --dump-outputs)
     for k in range(a.steps):
         set_input(pipe, k)
-        pipe.run(marks=marks[k], check_device=False)
+        last = pipe.run(marks=marks[k], check_device=False)
     if hasattr(pipe, "flush"):
-        pipe.flush()        # pipelined: the last pass's limiter, inside the timed region
+        # pipelined: the last pass's limiter, inside the timed region
+        last = pipe.flush() or last
     torch.cuda.synchronize()
     if ws > 1:
         dist.barrier()
@@ -460,21 +521,26 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, kern_ms, dev_err = float(tt[0]), float(tt[1]), int(tt[2])
 
-    # HBM copy bandwidth measured in this process (roofline.achievable_peak,
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, pipe.result(), last if mode == "chain" else None, rank)
+
+    # --full: HBM copy bandwidth measured in this process (roofline.achievable_peak,
     # SURVEY §8(d)): the timed launch's input copied by tomatis_copy_probe
-    from tomatis_audio_processor_amd._lib import check as _check, lib as _lib, ptr as _ptr, stream_handle
-    cp_src = inputs[0][: min(inputs[0].numel() // 4, 1 << 27) * 4]  # <= 2 GiB, >> the MALL
-    cp_dst = torch.empty_like(cp_src)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for j in range(7):
-        if j == 2:
-            ev[0].record()
-        _check(_lib().tomatis_copy_probe(_ptr(cp_src), _ptr(cp_dst), cp_src.numel(), stream_handle()),
-               "copy_probe")
-    ev[1].record()
-    torch.cuda.synchronize()
-    copy_gbs = 2.0 * 4.0 * cp_src.numel() * 5 / (ev[0].elapsed_time(ev[1]) * 1e-3) / 1e9
-    del cp_dst
+    copy_gbs = None
+    if a.full:
+        from tomatis_audio_processor_amd._lib import check as _check, lib as _lib, ptr as _ptr, stream_handle
+        cp_src = inputs[0][: min(inputs[0].numel() // 4, 1 << 27) * 4]  # <= 2 GiB, >> the MALL
+        cp_dst = torch.empty_like(cp_src)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for j in range(7):
+            if j == 2:
+                ev[0].record()
+            _check(_lib().tomatis_copy_probe(_ptr(cp_src), _ptr(cp_dst), cp_src.numel(), stream_handle()),
+                   "copy_probe")
+        ev[1].record()
+        torch.cuda.synchronize()
+        copy_gbs = 2.0 * 4.0 * cp_src.numel() * 5 / (ev[0].elapsed_time(ev[1]) * 1e-3) / 1e9
+        del cp_dst
 
     # a job of ONE file: unpipelined passes of the same workload (each ends with
     # its own limiter), their own pipeline; the headline above is a pipeline of
@@ -510,21 +576,23 @@ def main():
                        "limiter), no previous file to overlap with"}
         del p1
 
-    # per-stream manifest: (rank, stream, frames, C2 frames, max chunk peak bits)
-    res = pipe.result()
-    recs = []
-    for i in range(nstr):
-        st = res.states[res.frame_base[i]:res.frame_base[i] + res.n_frames[i]]
-        pk = res.chunk_peaks[res.chunk_base[i]:res.chunk_base[i] + res.n_chunks[i]].max()
-        recs.append(torch.stack([torch.tensor(rank, device="cuda"), torch.tensor(i, device="cuda"),
-                                 torch.tensor(res.n_frames[i], device="cuda"),
-                                 (st == 2).sum(), pk.to(torch.int64)]))
-    man = torch.stack(recs).to(torch.int64)
-    if ws > 1:
-        allm = [torch.empty_like(man) for _ in range(ws)]
-        dist.all_gather(allm, man)
-        man = torch.cat(allm)
-    man = man.cpu().numpy()
+    # --full: per-stream manifest: (rank, stream, frames, C2 frames, max chunk peak bits)
+    man = None
+    if a.full:
+        res = pipe.result()
+        recs = []
+        for i in range(nstr):
+            st = res.states[res.frame_base[i]:res.frame_base[i] + res.n_frames[i]]
+            pk = res.chunk_peaks[res.chunk_base[i]:res.chunk_base[i] + res.n_chunks[i]].max()
+            recs.append(torch.stack([torch.tensor(rank, device="cuda"), torch.tensor(i, device="cuda"),
+                                     torch.tensor(res.n_frames[i], device="cuda"),
+                                     (st == 2).sum(), pk.to(torch.int64)]))
+        man = torch.stack(recs).to(torch.int64)
+        if ws > 1:
+            allm = [torch.empty_like(man) for _ in range(ws)]
+            dist.all_gather(allm, man)
+            man = torch.cat(allm)
+        man = man.cpu().numpy()
 
     strong = mode == "timeshard"
     samples_per_step = n * ch * nstr * (1 if strong else ws)
@@ -539,7 +607,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if a.cpu_sample_s > 0 and mode == "standard" and not strong:
+        if a.full and a.cpu_sample_s > 0 and mode == "standard" and not strong:
             xs = ss.x[:a.cpu_sample_s * sr * ch].cpu().numpy().reshape(-1, ch)
             cpu = cpu_baseline(a.cpu_sample_s, sr, n_fft, hop, ch, x_host=xs, pool_s=a.cpu_pool_s)
             if a.cpu_file_s > 0:
@@ -565,8 +633,8 @@ def main():
             "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "achievable_peak": round(copy_gbs, 1),
-                         "frac_achievable": round(achieved_gbs / copy_gbs, 4),
+                         "achievable_peak": round(copy_gbs, 1) if copy_gbs else None,
+                         "frac_achievable": round(achieved_gbs / copy_gbs, 4) if copy_gbs else None,
                          "achievable_how": "tomatis_copy_probe (16-byte streaming copy) of the "
                                            "launch's input in this process, read + write bytes",
                          "kernel": "k_stft_ola (fused frame/window/FFT/gain/IFFT/OLA/normalise + per-chunk limiter)",
@@ -580,7 +648,9 @@ def main():
             "one_file_job": one,
             "cpu_baseline": cpu,
             "manifest": {"streams": int(man.shape[0]),
-                         "c2_fraction": round(float(man[:, 3].sum() / max(1, man[:, 2].sum())), 4)},
+                         "c2_fraction": round(float(man[:, 3].sum() / max(1, man[:, 2].sum())), 4)}
+                        if man is not None else None,
+            "full": bool(a.full),
         }
         print(json.dumps(out), flush=True)
     if ws > 1:
