@@ -179,6 +179,13 @@ __device__ void partner_tail(const MainArgs& A, int pr, int HOP, int N, int p_le
   tail(max(s_kaP + (int64_t)max(p_done, p_lead) * HOP, SP.out_begin) - SP.out_begin, hi);
 }
 
+// an opaque copy of a wave-uniform value (no instruction): what is derived from
+// it is computed at its use, not hoisted out of the frame loop and kept live
+__device__ __forceinline__ uint32_t opaque_s(uint32_t v) {
+  __asm__ volatile("" : "+s"(v));
+  return v;
+}
+
 template <int CH>
 __device__ __forceinline__ cf load_cf(const float* xs, int64_t p) {
   if constexpr (CH == 2) {
@@ -642,15 +649,18 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
   // non-monotone steps, rarely non-empty) are read from the stream table only
   // when present, so the frame loop does not hold 10 more SGPRs
   const uint32_t g_on = S.on_bits, g_off = S.off_bits;
-  const bool g_exc = (S.n_on_exc | S.n_off_exc) != 0;
+  // (one SGPR, compared at its use: as a bool it is a 64-bit lane mask that
+  // the frame loop spills and reads back every frame)
+  const uint32_t g_nexc = (uint32_t)(S.n_on_exc | S.n_off_exc);
   // frame k from its r: predicate, state (and alpha); r, state (alpha) of
   // emitted frames stored by lane 0; the gain row
-  auto gate_r = [&](float r, int64_t k, bool emit) -> uint32_t {
+  // (r_o / st_o / a_o: the frame's slots of A.r_out / A.st_out / A.a_out)
+  auto gate_r = [&](float r, float* r_o, uint8_t* st_o, double* a_o, bool emit) -> uint32_t {
     // r is wave-uniform: its bits through readfirstlane keep the predicate and
     // the automaton in SGPRs / SALU
     const uint32_t b = __builtin_amdgcn_readfirstlane(__float_as_uint(r));
     uint32_t pr;
-    if (g_exc) {
+    if (opaque_s(g_nexc) != 0) {
       pr = __builtin_amdgcn_readfirstlane(gate_pred(__uint_as_float(b), A.st[opaque(R.s)]));
     } else {
       pr = ((b & 0x7fffffffu) > 0x7f800000u) ? 0u : ((b >= g_on ? 1u : 0u) | (b <= g_off ? 2u : 0u));
@@ -669,19 +679,18 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
       }
     }
     if (emit && L == 0) {
-      const int64_t fo = S.frame_base + k;
-      A.r_out[fo] = r;
-      A.st_out[fo] = (uint8_t)(c2 ? 2 : 1);
+      *r_o = r;
+      *st_o = (uint8_t)(c2 ? 2 : 1);
       if constexpr (GX) {
-        if (A.gate_xf >= 0) A.a_out[fo] = alpha;
+        if (A.gate_xf >= 0) *a_o = alpha;
       }
     }
     return row;
   };
   // frame k: leaves of its newest block (the last SH registers of fr), r, gate
-  auto gate_frame = [&](const cf (&fr)[NR], int64_t k, bool emit) -> uint32_t {
+  auto gate_frame = [&](const cf (&fr)[NR], float* r_o, uint8_t* st_o, bool emit) -> uint32_t {
     lw = lv_window<SH, true>(lw, lv_leaves<CH, SH, NR>(fr, lscr, L));
-    return gate_r(lv_frame_r(lw), k, emit);
+    return gate_r(lv_frame_r(lw), r_o, st_o, nullptr, emit);
   };
   // n_fft 4096: lv_put128 of the frame's newest block went to s_lv and a pair
   // barrier ordered both waves' writes before this (both waves read every leaf
@@ -691,7 +700,8 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
   float* const lv2 = s_lv + (GX ? seq * SH * kL2LS : 0);
   auto gate_frame128 = [&](int64_t k, bool emit) -> uint32_t {
     lw = lv_window32<SH, true>(lw, lv_chains128<SH>(lv2, Lw), Lw);
-    return gate_r(lv_frame_r32(lw), k, emit);
+    const int64_t fo = S.frame_base + k;
+    return gate_r(lv_frame_r32(lw), A.r_out + fo, A.st_out + fo, A.a_out + fo, emit);
   };
   // n_fft 4096, the run's first frame: the leaves of its first NBLK - 1 blocks
   // (two pair barriers per block: written by both waves, read by both)
@@ -861,8 +871,18 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
     const int64_t s0 = S.first_start + kfirst * HOP;
     const __amdgpu_buffer_rsrc_t rx =
         mk_rsrc(xs + CH * s0, (uint32_t)(((int64_t)(nit - 1) * HOP + N) * CH * 4));
-    const __amdgpu_buffer_rsrc_t ry =
-        mk_rsrc(ys + CH * (s_ka - S.out_begin), (uint32_t)((int64_t)(nit - nwarm) * HOP * CH * 4));
+    // output: one base for the run; warm-up frames store to a resource of size
+    // zero, which drops their stores.  The gated kernels, short of SGPRs, give
+    // the run's resource a zero size word for them (no second resource to
+    // hold); the others, at their VGPR limit (hop 1024: 256, and that form
+    // costs it six spilled VGPRs), keep a null resource of their own
+    float* const yrun = ys + CH * (s_ka - S.out_begin);
+    const uint32_t ybytes = (uint32_t)((int64_t)(nit - nwarm) * HOP * CH * 4);
+    const __amdgpu_buffer_rsrc_t ry = mk_rsrc(yrun, ybytes), rnull = mk_rsrc(ys, 0u);
+    auto ry_of = [&](bool emit) {
+      if constexpr (GT) return mk_rsrc(yrun, emit ? ybytes : 0u);
+      else return emit ? ry : rnull;
+    };
     // gain-row ids through the scalar cache: the aligned 32-bit word holding the
     // frame's u16 id, loaded one frame ahead (s_load: lgkmcnt, so waiting for it
     // never waits for this wave's vector stores as an in-order vmcnt wait would)
@@ -894,7 +914,6 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
 #pragma unroll
       for (int j = 0; j < SH; ++j) dst[j] = bload<CH>(rx, L * CH * 4, so + P * j * CH * 4);
     };
-    const __amdgpu_buffer_rsrc_t rnull = mk_rsrc(ys, 0u);
     float wv[SHQ];
 #pragma unroll
     for (int q = 0; q < SHQ / 4; ++q) {
@@ -932,10 +951,18 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
       for (int j = 0; j < SH; ++j) v[NO + j] = t[j];
 #pragma unroll
       for (int i = 0; i < SH; ++i) o[i] = cf{0.f, 0.f};
-      store_out(o, rnull, 0);
+      store_out(o, ry_of(false), 0);
       ld_new(min(1, nit - 1), nh);
     }
     if constexpr (GT) lw = start_window(v);
+    // the frame's slots of r_out / st_out: one pointer each, stepped per frame
+    float* r_o = A.r_out + fb;
+    uint8_t* st_o = A.st_out + fb;
+    // the chunk walk in loop iterations (32-bit: a run is at most 2^20 frames)
+    const int64_t nck = next_chunk_k - kfirst;
+    int next_chunk_it =
+        __builtin_amdgcn_readfirstlane(nck < 0 ? -1 : (nck > INT_MAX ? INT_MAX : (int)nck));
+    const int chunk_it_step = (int)(chunk_k_step > INT_MAX / 2 ? INT_MAX / 2 : chunk_k_step);
     for (int it = 0; it < nit; ++it) {
       const bool emit = it >= nwarm;
       uint32_t row;
@@ -947,7 +974,9 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
         // quiet C2 -6 %: DESIGN.md §6, profiles/r06/prio/); back to 0 after
         // the forward FFT (transform)
         __builtin_amdgcn_s_setprio(2);
-        row = gate_frame(v, kfirst + it, emit);
+        row = gate_frame(v, r_o, st_o, emit);
+        ++r_o;
+        ++st_o;
       } else {
         row = row_of(rw_nx, it);
         rw_nx = row_word(min(it + 1, nit - 1));
@@ -955,24 +984,28 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
       if constexpr (PL) {
         // piece it of the partner -> LDS slot (branch-free: past the list the
         // resource is empty, the load returns zeros and the store drops)
+        // (the instruction's immediate offset applies to the buffer address and
+        // to the LDS address alike: one M0 value and no offset registers)
         const int blk = (int)plist[2 + 2 * pent(it)];
         const __amdgpu_buffer_rsrc_t rpl =
             mk_rsrc(yP + (int64_t)blk * (HOP * CH), it < np ? (uint32_t)HOPB : 0u);
-#pragma unroll
-        for (int u = 0; u < BQ; ++u)
+        static_assert(!PL || (BQ - 1) * 1024 < 4096, "12-bit immediate offset");
+        sfor<0, BQ>([&](auto uu) {
+          constexpr int U = decltype(uu)::value;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(
-              rpl, (__attribute__((address_space(3))) void*)(pslot + u * 1024), 16, L * 16,
-              u * 1024, 0, 2);
+              rpl, (__attribute__((address_space(3))) void*)pslot, 16, L * 16, 0, U * 1024, 2);
+        });
       }
       TPROF(0, v[0].x);
       transform(v, [&] { return row; });
       TPROF(5, v[NR - 1].x);
       // a frame that starts a new chunk flushes the previous chunk's peak first
       // (pk holds frames < k only)
-      if (emit && kfirst + it == next_chunk_k) {
+      if (emit && it == next_chunk_it) {
         flush_peak<P>(pk, cid, S, A.peaks, L, done);
         ++cid;
-        next_chunk_k = (cid < S.n_chunks - 1) ? next_chunk_k + chunk_k_step : INT64_MAX;
+        // (no overflow: next_chunk_it == it < nit here)
+        next_chunk_it = (cid < S.n_chunks - 1) ? next_chunk_it + chunk_it_step : INT_MAX;
       }
       // outputs of this frame's first hop: interior 1/sum w^2 (per lane, loaded
       // once before the loop), output scale, peak
@@ -993,7 +1026,7 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
       // prefetch's issue, where it waits for that HBM load
 #pragma unroll
       for (int j = 0; j < SH; ++j) v[NO + j] = cf{opaque_f(nh[j].x), opaque_f(nh[j].y)};
-      store_out(o, emit ? ry : rnull, emit ? (it - nwarm) * (HOP * CH * 4) : 0);
+      store_out(o, ry_of(emit), emit ? (it - nwarm) * (HOP * CH * 4) : 0);
       ld_new(min(it + 2, nit - 1), nh);
       if constexpr (PL) {
         // piece it: scale, store (its LDS-DMA is counted by vmcnt only)
@@ -1012,7 +1045,7 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
           const f4v t = *reinterpret_cast<const f4v*>(pslot + u * 1024 + L * 16) * sc;
           const f32x4 b = {__float_as_uint(t.x), __float_as_uint(t.y), __float_as_uint(t.z),
                            __float_as_uint(t.w)};
-          __builtin_amdgcn_raw_buffer_store_b128(b, rps, L * 16, u * 1024, 2);
+          __builtin_amdgcn_raw_buffer_store_b128(b, rps, L * 16 + u * 1024, 0, 2);
           // a 16-byte store reads its data VGPRs after issue: one wait state
           // before any VALU write of them (hipcc scheduled the next piece's
           // product into the same registers directly behind the store, and the
@@ -1127,7 +1160,8 @@ __global__ __launch_bounds__(WG, WG / 256 > 2 ? WG / 256 : 2) void k_stft_ola(Ma
         if constexpr (GT) {
           if (it == 0) lw = start_window(v);
           __builtin_amdgcn_s_setprio(2);  // (as the interior loop: until after the forward FFT)
-          row = gate_frame(v, k, live && k >= R.ka);
+          row = gate_frame(v, A.r_out + (S.frame_base + k), A.st_out + (S.frame_base + k),
+                           live && k >= R.ka);
         }
         transform(v, [&] { return row; });
       }

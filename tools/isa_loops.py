@@ -1,8 +1,11 @@
 """Instruction mix of the loops of one kernel in a hipcc -S listing (diagnostic).
 
-usage: python tools/isa_loops.py file.s [kernel-substring]
+usage: python tools/isa_loops.py file.s [kernel-substring] [--at TEXT]
 Prints, per loop (back-edge), its length and the counts of VALU / packed /
-v_mov / LDS / VMEM / scalar / waitcnt / scratch instructions.
+v_mov / lane (v_readlane / v_writelane: SGPR spill traffic, apart from the few
+the source asks for) / LDS / VMEM / scalar / s_nop / waitcnt / scratch
+instructions.  --at TEXT: only the innermost loop holding the first line that
+contains TEXT (the interior frame loop: --at "s_setprio 2").
 """
 import collections
 import re
@@ -25,6 +28,8 @@ def mix(seg):
             c['v_pk'] += 1
         elif op.startswith('v_mov') or op.startswith('v_accvgpr'):
             c['v_mov'] += 1
+        elif op.startswith(('v_readlane', 'v_writelane')):
+            c['lane'] += 1
         elif op.startswith('v_'):
             c['valu'] += 1
         elif op.startswith('ds_'):
@@ -35,6 +40,8 @@ def mix(seg):
             c['scratch'] += 1
         elif op.startswith('s_waitcnt'):
             c['waitcnt'] += 1
+        elif op.startswith('s_nop'):
+            c['s_nop'] += 1
         elif op.startswith('s_'):
             c['salu'] += 1
     return c
@@ -42,7 +49,7 @@ def mix(seg):
 
 def main():
     s = open(sys.argv[1]).read()
-    body = kernel_body(s, sys.argv[2] if len(sys.argv) > 2 else 'k_stft_ola')
+    body = kernel_body(s, sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != '--at' else 'k_stft_ola')
     lines = body.split('\n')
     labels = {}
     for i, l in enumerate(lines):
@@ -56,6 +63,10 @@ def main():
             loops.append((labels[mm.group(1)], i, mm.group(1)))
     code = [l.strip() for l in lines if l.strip() and not l.strip().startswith(('.', ';'))]
     print('whole kernel', len(code), dict(mix(code)))
+    if '--at' in sys.argv:
+        text = sys.argv[sys.argv.index('--at') + 1]
+        at = [i for i, l in enumerate(lines) if text in l][0]
+        loops = sorted((x for x in loops if x[0] <= at <= x[1]), key=lambda x: x[1] - x[0])[:1]
     for a, b, t in sorted(loops, key=lambda x: x[0] - x[1])[:8]:
         seg = [l.strip() for l in lines[a:b + 1]
                if l.strip() and not l.strip().startswith(('.', ';'))]
