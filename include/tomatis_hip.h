@@ -566,6 +566,54 @@ int tomatis_cal_gate_grid(const float* levels, int32_t n_fit, const int64_t* sta
                           const int32_t* target, const TomatisGateCand* cands, int32_t n_cand,
                           int32_t* out, uint8_t* states, void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * De-click stage (src/declick_inpaint.py; tm_declick.hip).
+ * x float32 [n_frames][ch] interleaved, ch in [1, 128].  Bit-exact: the host
+ * forms only the scalars of mad_sigma (:7-11) and thr = k * sigma (:68) from
+ * the bit patterns tomatis_declick_select returns.  All buffers device-resident.
+ * ------------------------------------------------------------------------- */
+
+/* Workspace (uint32 words, 16-byte aligned) of the calls below for a file of
+ * n_frames frames. */
+int64_t tomatis_declick_work_words(int64_t n_frames);
+
+/* dmax[i] = max_c |x[i+1][c] - x[i][c]| in float32, i < n_frames - 1
+ * (np.diff / np.abs / np.max, :64-66). */
+int tomatis_declick_dmax(const float* x, int64_t n_frames, int32_t ch, float* dmax,
+                         void* hip_stream);
+
+/* Exact order statistics of n non-negative, non-NaN floats (np.median's
+ * np.partition, :9-10): out_bits[0] / [1] = bit patterns of the values of rank
+ * rank_lo <= rank_hi < n in ascending order.  centered != 0 selects over
+ * |v[i] - center| in float32 instead (the MAD's keys, :10).  n < 2^32. */
+int tomatis_declick_select(const float* v, int64_t n, int32_t centered, float center,
+                           int64_t rank_lo, int64_t rank_hi, uint32_t* work, uint32_t* out_bits,
+                           void* hip_stream);
+
+/* hit = dmax > thr over n = n_frames - 1 differences (:69) and the clusters of
+ * the padded, merged mask (:83-90, merge_runs :13-24): consecutive hits i < j
+ * share a segment iff j - i <= 2 pad + 1 + gap.  counts (int64[4]): [0] hits,
+ * [1] raw segments, [2] and [3] zeroed. */
+int tomatis_declick_hits(const float* dmax, int64_t n, uint32_t thr_bits, int64_t pad, int64_t gap,
+                         uint32_t* work, int64_t* counts, void* hip_stream);
+
+/* After tomatis_declick_hits with the same dmax, n, thr_bits, pad, gap, work
+ * and counts: the segments [max(0, a - pad), min(n + 1, b + 1 + pad)) of the
+ * clusters (first hit a, last hit b) no longer than max_fix (:92-93), ascending,
+ * as int64 [start, end) pairs in segs; counts[2] = kept.  raw = counts[1] as
+ * read by the caller; bounds: 2 raw int64 of scratch; segs: raw pairs.
+ * counts[3] != 0 (device error word): raw did not match the clusters found. */
+int tomatis_declick_segments(const float* dmax, int64_t n, uint32_t thr_bits, int64_t pad,
+                             int64_t gap, int64_t max_fix, uint32_t* work, int64_t raw,
+                             int64_t* bounds, int64_t* segs, int64_t* counts, void* hip_stream);
+
+/* inpaint_linear (:26-46) over disjoint segments at least one frame apart: y
+ * (a copy of x on entry) gets f32(f32(f32(1 - t) left) + f32(t right)) over
+ * [s, e) with left = x[s0], right = x[e0], s0 = max(0, s - 1),
+ * e0 = min(n_frames - 1, e), t = np.linspace(0, 1, e0 - s0 + 1, float32). */
+int tomatis_declick_inpaint(const float* x, float* y, int64_t n_frames, int32_t ch,
+                            const int64_t* segs, int64_t n_segs, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

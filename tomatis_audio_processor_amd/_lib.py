@@ -149,6 +149,16 @@ _SIGS = {
     "tomatis_an_band_energy": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "tomatis_cal_gate_grid": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    # de-click stage
+    "tomatis_declick_work_words": (C.c_int64, [C.c_int64]),
+    "tomatis_declick_dmax": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
+    "tomatis_declick_select": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_float, C.c_int64,
+                                         C.c_int64, _P, _P, _P]),
+    "tomatis_declick_hits": (C.c_int, [_P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P, _P,
+                                       _P]),
+    "tomatis_declick_segments": (C.c_int, [_P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64,
+                                           C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
+    "tomatis_declick_inpaint": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

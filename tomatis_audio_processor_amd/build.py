@@ -9,7 +9,9 @@ Six translation units, compiled in parallel and linked into one C-ABI library:
 * ``tm_analysis.hip``  analysis spectra for the validators / calibration tools
   (SURVEY.md §8 rows f3/f4);
 * ``tm_flacenc.hip``   FLAC frames encoded on the device (row f1's egress);
-* ``tm_flacdec.hip``   FLAC frames decoded on the device (row f1's ingest).
+* ``tm_flacdec.hip``   FLAC frames decoded on the device (row f1's ingest);
+* ``tm_declick.hip``   the de-click stage: MAD click detector and linear
+  inpainting (row f5; ``-ffp-contract=off`` like the gate unit: it is bit-exact).
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ UNITS = {  # source -> extra flags
     "tm_analysis.hip": [],
     "tm_flacenc.hip": [],
     "tm_flacdec.hip": [],
+    "tm_declick.hip": [],
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
                                         "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h")] + \
