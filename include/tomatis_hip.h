@@ -614,6 +614,41 @@ int tomatis_declick_segments(const float* dmax, int64_t n, uint32_t thr_bits, in
 int tomatis_declick_inpaint(const float* x, float* y, int64_t n_frames, int32_t ch,
                             const int64_t* segs, int64_t n_segs, void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * Alignment (find_delay_by_corr of
+ * src/layer2_analyze_eq.py:17-52, src/calibrate_to_baseline_v2.py:46-82 and
+ * src/compare_audio.py; tm_align.hip).  All buffers device-resident.
+ * ------------------------------------------------------------------------- */
+
+/* doubles behind out_mean of tomatis_align_envelope: [0] the mean, the rest
+ * scratch (the partial sums of a fixed-order reduction) */
+#define TOMATIS_ALIGN_MEAN_DOUBLES 1025
+
+/* The mean-free decimated power-mono envelope of frames [start, start + len)
+ * of the interleaved stereo float32 x (n_total frames), layer2_analyze_eq.py
+ * :31-33 / :43-45:  e[i] = sqrt(0.5 (l l + r r) + 1e-12) in float32 (power_mono,
+ * :9-11), zero outside [0, len) of the sub-range;
+ *   y[j] = sum_m taps[m] e[down j + (n_taps - 1) / 2 - m],  j < ceil(len / down),
+ * which is scipy.signal.resample_poly(e, 1, down) for taps =
+ * float32(firwin(20 down + 1, 1 / down, window=("kaiser", 5.0)));
+ * out_mean[0] = mean(y) (float64 sums in a fixed order), out[j] = y[j] -
+ * float32(mean).  2 <= down <= 64, n_taps odd and <= 20 down + 1; out: ceil(len /
+ * down) floats; out_mean: TOMATIS_ALIGN_MEAN_DOUBLES doubles. */
+int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
+                           int32_t down, const float* taps, int32_t n_taps, float* out,
+                           double* out_mean, void* hip_stream);
+
+/* out[k] = sum_j t[k + j] b[j], k <= nt - nb: fftconvolve(t, b[::-1], "valid")
+ * (:47) for nt >= nb, as direct float32 FMAs; sums of 256 taps are added in tap
+ * order, so the result is the same in every run. */
+int tomatis_align_xcorr(const float* t, int64_t nt, const float* b, int64_t nb, float* out,
+                        void* hip_stream);
+
+/* np.argmax (:48): out_index[0] = the lowest index of the largest c[i] (the
+ * first NaN if there is one), out_value[0] = c[index].  n < 2^32. */
+int tomatis_align_argmax(const float* c, int64_t n, int64_t* out_index, float* out_value,
+                         void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

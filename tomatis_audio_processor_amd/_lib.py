@@ -24,6 +24,7 @@ E_UNSUPPORTED = -2       # TOMATIS_E_UNSUPPORTED
 OPT_FUSE_LIMITER = 1     # TOMATIS_OPT_FUSE_LIMITER
 OPT_LIMITER_SPIN = 2     # TOMATIS_OPT_LIMITER_SPIN
 OPT_MINHOLD_SERIAL = 3   # TOMATIS_OPT_MINHOLD_SERIAL
+ALIGN_MEAN_DOUBLES = 1025  # TOMATIS_ALIGN_MEAN_DOUBLES
 # development overrides (TOMATIS_DEV_*: tests and A/B experiments only)
 DEV_KEYS = dict(FAST_LOOP=1, RUN_ROUNDS=2, RUN_FRAMES=3, LEVELS_LEGACY=4, GATE_TF=5, MH_PARTS=6,
                 FORCE_LDS=7, P64=8, ALPHA_SEQ=9, GAIN_LDS=10, FUSE_LIMITER=11, WG=12,
@@ -159,6 +160,11 @@ _SIGS = {
     "tomatis_declick_segments": (C.c_int, [_P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64,
                                            C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     "tomatis_declick_inpaint": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
+    # alignment
+    "tomatis_align_envelope": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P,
+                                         C.c_int32, _P, _P, _P]),
+    "tomatis_align_xcorr": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "tomatis_align_argmax": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -1,0 +1,194 @@
+"""Delay between a recording and a rendered file, on the device (SURVEY.md §8
+row f6): ``find_delay_by_corr`` of the reference's workflow scripts
+(src/layer2_analyze_eq.py:17-52, src/calibrate_to_baseline_v2.py:46-82).
+
+  reference (layer2_analyze_eq.py)               here
+  ---------------------------------------------- ------------------------------
+  power_mono :9-11, resample_poly(m, ds_sr, sr),  tomatis_align_envelope (one pass
+  ``-= np.mean`` :31-33 / :43-45                  over the PCM, polyphase FIR in LDS)
+  fftconvolve(mt_ds, mb_ds[::-1], "valid") :47    tomatis_align_xcorr (direct FMA)
+  np.argmax :48                                   tomatis_align_argmax
+  chunk bounds :23-27, centres and rounding       host (scalars)
+  :49-52
+
+The device path takes ``sr % ds_sr == 0`` with a decimation of 2..64.  Another
+ratio, and a target whose envelope is shorter than the base chunk's (scipy's
+``fftconvolve`` swaps its operands there), run the reference's scipy calls on
+the host (``_find_delay_host``).  Otherwise there is no CPU fallback.
+Inputs are numpy arrays, resident cuda tensors or file paths.
+"""
+from __future__ import annotations
+
+import functools
+import math
+
+import numpy as np
+
+from . import audio_io
+from ._lib import ALIGN_MEAN_DOUBLES, check, lib, ptr, stream_handle
+
+EPS = 1e-12
+MAX_DOWN = 64  # tm_align.hip kMaxDown
+
+
+def _torch():
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("alignment needs a ROCm GPU (MI355X); there is no CPU fallback")
+    return torch
+
+
+def _ratio(sr: int, ds_sr: int):
+    g = math.gcd(int(ds_sr), int(sr))
+    return int(ds_sr) // g, int(sr) // g  # up, down as resample_poly reduces them
+
+
+def device_ratio(sr: int, ds_sr: int) -> bool:
+    up, down = _ratio(sr, ds_sr)
+    return up == 1 and 2 <= down <= MAX_DOWN
+
+
+@functools.lru_cache(maxsize=8)
+def _taps(down: int) -> np.ndarray:
+    """resample_poly's own filter for up = 1 and float32 input."""
+    from scipy.signal import firwin
+    return firwin(20 * down + 1, 1.0 / down, window=("kaiser", 5.0)).astype(np.float32)
+
+
+def _load(a, sr):
+    """-> (array or cuda tensor [n, 2], is_tensor); the reference's asserts."""
+    if isinstance(a, str):
+        a, got = audio_io.read(a)
+        assert got == sr
+    is_tensor = not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+    if not is_tensor:
+        a = np.asarray(a)
+    assert a.ndim == 2 and a.shape[1] == 2
+    return a, is_tensor
+
+
+def _stereo_dev(a):
+    torch = _torch()
+    if isinstance(a, torch.Tensor):
+        return a.to(device="cuda", dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+
+
+def _vec_dev(a):
+    return _stereo_dev(a).reshape(-1)
+
+
+def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False):
+    """``m = resample_poly(power_mono(x_lr[start:stop]), ds_sr, sr).astype(float32);
+    m -= np.mean(m)`` as a cuda tensor (``with_mean``: and the mean removed)."""
+    torch = _torch()
+    if not device_ratio(sr, ds_sr):
+        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the device decimator takes sr % ds_sr == 0 "
+                         f"and a factor of 2..{MAX_DOWN}")
+    _, down = _ratio(sr, ds_sr)
+    x, is_tensor = _load(x_lr, sr)
+    n = x.shape[0]
+    stop = n if stop is None else min(int(stop), n)
+    start = int(start)
+    if not 0 <= start < stop:
+        raise ValueError("envelope_ds needs a non-empty range inside the signal")
+    ln = stop - start
+    if not is_tensor:  # a host array: only the range is uploaded
+        x, n, start = x[start:stop], ln, 0
+    xd = _stereo_dev(x)
+    taps = torch.from_numpy(_taps(down)).cuda()
+    out = torch.empty(-(-ln // down), dtype=torch.float32, device="cuda")
+    mean = torch.empty(ALIGN_MEAN_DOUBLES, dtype=torch.float64, device="cuda")
+    check(lib().tomatis_align_envelope(ptr(xd), n, start, ln, down, ptr(taps), taps.numel(),
+                                       ptr(out), ptr(mean), stream_handle()), "align_envelope")
+    return (out, float(mean[0].item())) if with_mean else out
+
+
+def xcorr_valid(t, b):
+    """``fftconvolve(t, b[::-1], mode="valid")`` for len(t) >= len(b): cuda tensor."""
+    torch = _torch()
+    td, bd = _vec_dev(t), _vec_dev(b)
+    nt, nb = td.numel(), bd.numel()
+    if nb < 1 or nt < nb:
+        raise ValueError("xcorr_valid needs 1 <= len(b) <= len(t)")
+    out = torch.empty(nt - nb + 1, dtype=torch.float32, device="cuda")
+    check(lib().tomatis_align_xcorr(ptr(td), nt, ptr(bd), nb, ptr(out), stream_handle()),
+          "align_xcorr")
+    return out
+
+
+def argmax_first(c, with_value=False):
+    """``int(np.argmax(c))``: the lowest index of the maximum."""
+    torch = _torch()
+    cd = _vec_dev(c)
+    idx = torch.empty(1, dtype=torch.int64, device="cuda")
+    val = torch.empty(1, dtype=torch.float32, device="cuda")
+    check(lib().tomatis_align_argmax(ptr(cd), cd.numel(), ptr(idx), ptr(val), stream_handle()),
+          "align_argmax")
+    k = int(idx.item())
+    return (k, float(val.item())) if with_value else k
+
+
+def _chunk(nbase: int, sr: int, chunk_sec):
+    """The middle chunk_sec of the base, clamped to the file (:23-27)."""
+    mid = int(0.5 * nbase)
+    half = int(0.5 * chunk_sec * sr)
+    return max(0, mid - half), min(nbase, mid + half)
+
+
+def _delay(k: int, n_ds: int, s: int, e: int, sr: int, ds_sr: int) -> int:
+    """:49-52."""
+    base_center_sec = (s + (e - s) // 2) / sr
+    targ_center_sec = (k + n_ds // 2) / ds_sr
+    delay_sec = targ_center_sec - base_center_sec
+    return int(round(delay_sec * sr))
+
+
+def power_mono(x_lr: np.ndarray) -> np.ndarray:
+    """layer2_analyze_eq.py:9-11 (host)."""
+    p = 0.5 * (x_lr[:, 0] * x_lr[:, 0] + x_lr[:, 1] * x_lr[:, 1])
+    return np.sqrt(p + EPS)
+
+
+def _host(a):
+    return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
+
+
+def _find_delay_host(target, base, sr=48000, ds_sr=2000, chunk_sec=25):
+    """The reference's own scipy calls on the host (:17-52), for the cases the
+    device path leaves out."""
+    from scipy.signal import fftconvolve, resample_poly
+    xt, _ = _load(target, sr)
+    xb, _ = _load(base, sr)
+    xt, xb = _host(xt).astype(np.float32, copy=False), _host(xb).astype(np.float32, copy=False)
+    s, e = _chunk(len(xb), sr, chunk_sec)
+    mb = power_mono(xb[s:e])
+    mb_ds = resample_poly(mb, ds_sr, sr).astype(np.float32)
+    mb_ds = mb_ds - np.mean(mb_ds)
+    mt = power_mono(xt).astype(np.float32)
+    mt_ds = resample_poly(mt, ds_sr, sr).astype(np.float32)
+    mt_ds = mt_ds - np.mean(mt_ds)
+    corr = fftconvolve(mt_ds, mb_ds[::-1], mode="valid")
+    k = int(np.argmax(corr))
+    return _delay(k, len(mb_ds), s, e, sr, ds_sr)
+
+
+def find_delay(target, base, sr=48000, ds_sr=2000, chunk_sec=25):
+    """delay = target - base in samples (positive: the target starts later),
+    layer2_analyze_eq.find_delay_by_corr (:17-52)."""
+    xt, _ = _load(target, sr)
+    xb, _ = _load(base, sr)
+    s, e = _chunk(len(xb), sr, chunk_sec)
+    if not device_ratio(sr, ds_sr):
+        return _find_delay_host(xt, xb, sr, ds_sr, chunk_sec)
+    _, down = _ratio(sr, ds_sr)
+    if e <= s or len(xt) < 1 or -(-len(xt) // down) < -(-(e - s) // down):
+        return _find_delay_host(xt, xb, sr, ds_sr, chunk_sec)
+    mb_ds = envelope_ds(xb, sr, ds_sr, s, e)
+    mt_ds = envelope_ds(xt, sr, ds_sr)
+    k = argmax_first(xcorr_valid(mt_ds, mb_ds))
+    return _delay(k, mb_ds.numel(), s, e, sr, ds_sr)
+
+
+__all__ = ["envelope_ds", "xcorr_valid", "argmax_first", "find_delay", "device_ratio",
+           "power_mono"]

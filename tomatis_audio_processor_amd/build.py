@@ -1,6 +1,6 @@
 """Build ``libtomatis_hip.so`` in-tree with hipcc for gfx950 (no cmake/ninja needed).
 
-Six translation units, compiled in parallel and linked into one C-ABI library:
+Seven translation units, compiled in parallel and linked into one C-ABI library:
 
 * ``tm_kernels.hip``   levels, gate, limiter, plan and the ``extern "C"`` entry points;
 * ``tm_transform.hip`` the fused transform kernels (FMA contraction on;
@@ -11,7 +11,9 @@ Six translation units, compiled in parallel and linked into one C-ABI library:
 * ``tm_flacenc.hip``   FLAC frames encoded on the device (row f1's egress);
 * ``tm_flacdec.hip``   FLAC frames decoded on the device (row f1's ingest);
 * ``tm_declick.hip``   the de-click stage: MAD click detector and linear
-  inpainting (row f5; ``-ffp-contract=off`` like the gate unit: it is bit-exact).
+  inpainting (row f5; ``-ffp-contract=off`` like the gate unit: it is bit-exact);
+* ``tm_align.hip``     the delay estimate: power-mono envelope decimator,
+  direct cross-correlation, arg-max (row f6).
 """
 from __future__ import annotations
 
@@ -35,6 +37,7 @@ UNITS = {  # source -> extra flags
     "tm_flacenc.hip": [],
     "tm_flacdec.hip": [],
     "tm_declick.hip": [],
+    "tm_align.hip": [],
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
                                         "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h")] + \

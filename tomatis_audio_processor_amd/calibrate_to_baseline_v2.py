@@ -16,8 +16,9 @@ reference; the per-frame and per-candidate work runs in ``libtomatis_hip.so``:
                                                mismatch / switch counts
   debounce_state :111-128, kmeans2_1d :33-44,  host (once per file, O(frames),
   medfilt, the score / arg-min :258-265        same numpy/scipy calls)
-  find_delay_by_corr :46-82                    host scipy (resample_poly,
-                                               fftconvolve), as the reference
+  find_delay_by_corr :46-82                    align.find_delay: envelope decimator,
+                                               direct correlation and arg-max in
+                                               tm_align.hip
 
 The argmin is taken on the host from the device's exact integer counts in the
 reference's own loop order with its own float64 score, so ``best`` is the
@@ -148,28 +149,9 @@ def debounce_state(state: np.ndarray, min_run: int = 3) -> np.ndarray:
 
 def find_delay_by_corr(orig_path, base_path, sr=48000, ds_sr=2000, chunk_sec=25):
     """calibrate_to_baseline_v2.py:46-82: delay (orig - base) in samples from the
-    cross-correlation of 2 kHz power-mono envelopes (host scipy, as the reference)."""
-    from scipy.signal import fftconvolve, resample_poly
-    xo, sro = audio_io.read(orig_path)
-    xb, srb = audio_io.read(base_path)
-    assert sro == sr and srb == sr
-    assert xo.shape[1] == 2 and xb.shape[1] == 2
-    nbase = len(xb)
-    mid = int(0.5 * nbase)
-    half = int(0.5 * chunk_sec * sr)
-    s = max(0, mid - half)
-    e = min(nbase, mid + half)
-    mb = power_mono(xb[s:e])
-    mb_ds = resample_poly(mb, ds_sr, sr).astype(np.float32)
-    mb_ds = mb_ds - np.mean(mb_ds)
-    mo = power_mono(xo).astype(np.float32)
-    mo_ds = resample_poly(mo, ds_sr, sr).astype(np.float32)
-    mo_ds = mo_ds - np.mean(mo_ds)
-    corr = fftconvolve(mo_ds, mb_ds[::-1], mode="valid")
-    k = int(np.argmax(corr))
-    base_center = (s + (e - s) // 2) / sr
-    orig_center = (k + len(mb_ds) // 2) / ds_sr
-    return int(round((orig_center - base_center) * sr))
+    cross-correlation of 2 kHz power-mono envelopes, on the device (align.py)."""
+    from . import align
+    return align.find_delay(orig_path, base_path, sr=sr, ds_sr=ds_sr, chunk_sec=chunk_sec)
 
 
 def _grid(levels_rows, starts, target, cands, want_states=False):

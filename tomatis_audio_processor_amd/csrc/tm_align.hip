@@ -1,0 +1,347 @@
+// tm_align.hip — delay estimation on the device.
+//
+// find_delay_by_corr of the reference's workflow scripts
+// (src/layer2_analyze_eq.py:17-52, src/calibrate_to_baseline_v2.py:46-82) as
+// three kernel groups, each behind its own entry point:
+//   power_mono + resample_poly(e, 1, down) + "-= mean"   :31-33,43-45 -> k_al_envelope,
+//                                                           k_al_sum, k_al_center
+//   fftconvolve(mt_ds, mb_ds[::-1], "valid")             :47      -> k_al_xcorr
+//   np.argmax                                            :48      -> k_al_argmax, k_al_decode
+//
+// Layout (wave64, 256-thread workgroups):
+//  * envelope: a workgroup owns T consecutive outputs (T = blockDim.x).  It
+//    stages the down (T - 1) + n_taps envelope samples they read, formed from
+//    8-byte stereo loads (the PCM is read once; the halo of neighbouring
+//    workgroups comes from L2), in LDS as [phase][Q]: sample g0 + i lies at
+//    (i % down) * Q + i / down.  Tap u of output j then reads phase u % down at
+//    column j + u / down: consecutive lanes read consecutive words (no bank
+//    conflict), the tap itself is uniform (a scalar load).  Q is odd, so the
+//    staging stores of consecutive samples (stride Q) spread over the banks.
+//  * mean: a fixed grid of at most kSumGroups workgroups writes float64
+//    partial sums (grid-stride, fixed order), every workgroup of the centring
+//    pass adds them up in index order: the same mean in every workgroup and in
+//    every run, no float atomics.
+//  * correlation: direct float32 FMA.  A lane owns kR = 16 consecutive outputs
+//    and slides a 32-word register window of t over the template: 16 new words
+//    (four 16-byte LDS reads) and 16 template words (uniform LDS reads) feed
+//    256 FMAs.  The workgroup's kT * kR outputs walk the template in blocks of
+//    kJB taps staged in LDS (t window and template block, zero-filled past the
+//    ends, so the inner loop has no bounds); sums run over kSB taps at a time
+//    and are added to the running total in tap order, which keeps the float32
+//    rounding of a 50 000-tap sum near sqrt(kSB) + sqrt(nb / kSB) ulps and the
+//    result identical from run to run.  The t window is stored with four words
+//    of padding after every 16 (lane stride 80 B): the 16-byte reads of the 16
+//    lanes of one LDS group start on distinct multiples of four banks.
+//  * argmax: 64-bit keys (order-preserving value bits << 32 | ~index): the
+//    integer maximum is the largest value at the lowest index (np.argmax's
+//    rule; NaN ranks above everything, as numpy's first NaN).  Per-lane keys,
+//    wave and workgroup maxima, one integer atomic per workgroup.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/tomatis_hip.h"
+
+namespace {
+
+typedef long long i64;
+typedef unsigned long long u64;
+
+constexpr int kT = 256;                   // threads per workgroup
+constexpr int kSumGroups = TOMATIS_ALIGN_MEAN_DOUBLES - 1;  // partial sums of the mean
+constexpr int kMaxDown = 64;
+constexpr int kLdsBytes = 48 * 1024;      // envelope staging budget
+constexpr int kR = 16;                    // outputs per lane of the correlation
+constexpr int kOut = kT * kR;             // outputs per workgroup
+constexpr int kJB = 1024;                 // template block staged in LDS
+constexpr int kSB = 256;                  // taps per float32 partial sum
+constexpr int kWin = kOut + kJB;          // t words staged per block
+constexpr int kWinPad = kWin / 16 * 20;   // with 4 words of padding per 16
+
+int al_fail(hipError_t e) { return e == hipSuccess ? TOMATIS_OK : TOMATIS_E_HIP; }
+int al_launch() { return al_fail(hipGetLastError()); }
+
+int al_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      cus < 1)
+    cus = 256;
+  return cus;
+}
+
+// ---------------------------------------------------------------------------
+// envelope: e = sqrt(0.5 (l l + r r) + 1e-12) in float32, decimating FIR
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float power_mono(float l, float r) {
+  const float p = __fmul_rn(0.5f, __fadd_rn(__fmul_rn(l, l), __fmul_rn(r, r)));
+  return sqrtf(__fadd_rn(p, 1e-12f));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_al_envelope(const float* __restrict__ x, i64 len, int down,
+                                                     const float* __restrict__ taps, int n_taps,
+                                                     int Q, float* __restrict__ out, i64 n_out) {
+  extern __shared__ float stage[];  // [down][Q]
+  const int T = blockDim.x, tid = threadIdx.x;
+  const i64 j0 = (i64)blockIdx.x * T;
+  const int half = (n_taps - 1) / 2;
+  const i64 g0 = (i64)down * j0 - half;
+  const int cnt = down * (T - 1) + n_taps;
+  for (int i = tid; i < cnt; i += T) {
+    const i64 g = g0 + i;
+    float e = 0.0f;  // the sub-range is a signal of its own: zeros outside it
+    if (g >= 0 && g < len) {
+      if constexpr (VEC) {
+        const float2 v = *reinterpret_cast<const float2*>(x + 2 * g);
+        e = power_mono(v.x, v.y);
+      } else {
+        e = power_mono(x[2 * g], x[2 * g + 1]);
+      }
+    }
+    const int q = i / down;
+    stage[(i - q * down) * Q + q] = e;
+  }
+  __syncthreads();
+  const i64 j = j0 + tid;
+  if (j >= n_out) return;
+  // y[j] = sum_u taps[n_taps - 1 - u] e[down j - half + u], u = q down + p
+  const float* tp = taps + (n_taps - 1);
+  const int rows = n_taps / down, rem = n_taps - rows * down;
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;  // four chains, joined pairwise
+  for (int q = 0; q <= rows; ++q) {
+    const float* col = stage + tid + q;
+    const float* h = tp - q * down;
+    const int np = q < rows ? down : rem;
+    int p = 0;
+    for (; p + 4 <= np; p += 4) {
+      a0 = fmaf(h[-p], col[p * Q], a0);
+      a1 = fmaf(h[-p - 1], col[(p + 1) * Q], a1);
+      a2 = fmaf(h[-p - 2], col[(p + 2) * Q], a2);
+      a3 = fmaf(h[-p - 3], col[(p + 3) * Q], a3);
+    }
+    for (; p < np; ++p) a0 = fmaf(h[-p], col[p * Q], a0);
+  }
+  out[j] = (a0 + a1) + (a2 + a3);
+}
+
+// Sum over the workgroup in a fixed order; the result in every thread.  sm: kT / 64 slots.
+__device__ __forceinline__ double block_sum(double v, double* sm) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int i = 0; i < kT / 64; ++i) s += sm[i];
+  __syncthreads();
+  return s;
+}
+
+// part[g] = float64 sum of y[i], i = g kT + t (mod G kT), G = gridDim.x
+__global__ __launch_bounds__(kT) void k_al_sum(const float* __restrict__ y, i64 n,
+                                                double* __restrict__ part) {
+  __shared__ double sm[kT / 64];
+  double s = 0.0;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT)
+    s += (double)y[i];
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// y -= float32(sum(part) / n); mean[0] = sum(part) / n
+__global__ __launch_bounds__(kT) void k_al_center(float* __restrict__ y, i64 n,
+                                                   const double* __restrict__ part, int n_part,
+                                                   double* __restrict__ mean) {
+  __shared__ double sm[kT / 64];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_part; i += kT) s += part[i];
+  const double m = block_sum(s, sm) / (double)n;
+  const float mf = (float)m;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT)
+    y[i] = __fsub_rn(y[i], mf);
+  if (blockIdx.x == 0 && threadIdx.x == 0) mean[0] = m;
+}
+
+// ---------------------------------------------------------------------------
+// "valid" correlation c[k] = sum_j t[k + j] b[j]
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int win_at(int i) { return (i >> 4) * 20 + (i & 15); }
+
+// 16 taps: outputs r = 0..15 read window words (OFF + r + u) mod 32
+template <int OFF>
+__device__ __forceinline__ void taps16(float (&acc)[kR], const float (&w)[32],
+                                       const float* __restrict__ bb) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const float4 h = *reinterpret_cast<const float4*>(bb + 4 * v);
+    const float hh[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int r = 0; r < kR; ++r) acc[r] = fmaf(w[(OFF + r + 4 * v + k) & 31], hh[k], acc[r]);
+    }
+  }
+}
+
+template <int OFF>
+__device__ __forceinline__ void load16(float (&w)[32], const float* __restrict__ p) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const float4 a = *reinterpret_cast<const float4*>(p + 4 * v);
+    w[OFF + 4 * v] = a.x;
+    w[OFF + 4 * v + 1] = a.y;
+    w[OFF + 4 * v + 2] = a.z;
+    w[OFF + 4 * v + 3] = a.w;
+  }
+}
+
+__global__ __launch_bounds__(kT) void k_al_xcorr(const float* __restrict__ t, i64 nt,
+                                                  const float* __restrict__ b, i64 nb,
+                                                  float* __restrict__ c, i64 nc) {
+  __shared__ __attribute__((aligned(16))) float win[kWinPad];
+  __shared__ __attribute__((aligned(16))) float tb[kJB];
+  const int tid = threadIdx.x;
+  const i64 kb = (i64)blockIdx.x * kOut;
+  float tot[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) tot[r] = 0.0f;
+  for (i64 j0 = 0; j0 < nb; j0 += kJB) {
+    __syncthreads();  // the previous block's reads
+    for (int i = tid; i < kWin; i += kT) {
+      const i64 g = kb + j0 + i;
+      win[win_at(i)] = g < nt ? t[g] : 0.0f;
+    }
+    for (int i = tid; i < kJB; i += kT) tb[i] = j0 + i < nb ? b[j0 + i] : 0.0f;
+    __syncthreads();
+    const i64 left = nb - j0;
+    const int nsub = left >= kJB ? kJB / kSB : (int)((left + kSB - 1) / kSB);
+    for (int sbi = 0; sbi < nsub; ++sbi) {
+      const int s0 = sbi * kSB;
+      float acc[kR], w[32];
+#pragma unroll
+      for (int r = 0; r < kR; ++r) acc[r] = 0.0f;
+      // word i of this lane's window is t[kb + j0 + kR tid + i]: 16-word row tid + i / 16
+      const float* row = win + (tid + s0 / 16) * 20;
+      load16<0>(w, row);
+#pragma unroll 1
+      for (int s = 0; s < kSB; s += 32) {
+        load16<16>(w, row + (s / 16 + 1) * 20);
+        taps16<0>(acc, w, tb + s0 + s);
+        load16<0>(w, row + (s / 16 + 2) * 20);
+        taps16<16>(acc, w, tb + s0 + s + 16);
+      }
+#pragma unroll
+      for (int r = 0; r < kR; ++r) tot[r] += acc[r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    const i64 k = kb + (i64)tid * kR + r;
+    if (k < nc) c[k] = tot[r];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// argmax, the lowest index on ties
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ u64 arg_key(float v, i64 i) {
+  uint32_t u;
+  if (v != v) {
+    u = 0xFFFFFFFFu;  // NaN: above everything
+  } else {
+    u = __float_as_uint(v == 0.0f ? 0.0f : v);  // -0 == +0
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  }
+  return ((u64)u << 32) | (u64)(0xFFFFFFFFu - (uint32_t)i);
+}
+
+__global__ __launch_bounds__(kT) void k_al_argmax(const float* __restrict__ c, i64 n, u64* best) {
+  __shared__ u64 sm[kT / 64];
+  u64 m = 0;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT) {
+    const u64 k = arg_key(c[i], i);
+    m = k > m ? k : m;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 v = __shfl_xor(m, o, 64);
+    m = v > m ? v : m;
+  }
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < kT / 64; ++i) m = sm[i] > m ? sm[i] : m;
+    atomicMax(best, m);
+  }
+}
+
+__global__ void k_al_decode(const float* __restrict__ c, i64* index, float* value) {
+  const u64 k = *reinterpret_cast<const u64*>(index);
+  const i64 i = (i64)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFu));
+  *index = i;
+  *value = c[i];
+}
+
+bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
+                           int32_t down, const float* taps, int32_t n_taps, float* out,
+                           double* out_mean, void* hs) {
+  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
+      len > n_total - start || down < 2 || n_taps < 1 || (n_taps & 1) == 0)
+    return TOMATIS_E_ARG;
+  if (down > kMaxDown || n_taps > 20 * down + 1) return TOMATIS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hs;
+  const i64 n_out = (len + down - 1) / down;
+  // the largest of 256 / 128 / 64 outputs per workgroup whose staging fits
+  int T = kT, Q = 0;
+  for (;; T >>= 1) {
+    Q = (T + (n_taps - 1) / down) | 1;
+    if ((i64)down * Q * (i64)sizeof(float) <= kLdsBytes || T == 64) break;
+  }
+  const size_t lds = (size_t)down * Q * sizeof(float);
+  const i64 groups = (n_out + T - 1) / T;
+  if (groups > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
+  const float* xs = x + 2 * start;
+  if (aligned(xs, 8))
+    hipLaunchKernelGGL(k_al_envelope<true>, dim3((unsigned)groups), dim3(T), lds, s, xs, (i64)len,
+                       (int)down, taps, (int)n_taps, Q, out, n_out);
+  else
+    hipLaunchKernelGGL(k_al_envelope<false>, dim3((unsigned)groups), dim3(T), lds, s, xs,
+                       (i64)len, (int)down, taps, (int)n_taps, Q, out, n_out);
+  const i64 want = (n_out + kT - 1) / kT;
+  const int G = (int)(want < kSumGroups ? want : kSumGroups);
+  hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, out_mean + 1);
+  const i64 cap = (i64)al_cus() * 8;
+  hipLaunchKernelGGL(k_al_center, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, out,
+                     n_out, (const double*)(out_mean + 1), G, out_mean);
+  return al_launch();
+}
+
+int tomatis_align_xcorr(const float* t, int64_t nt, const float* b, int64_t nb, float* out,
+                        void* hs) {
+  if (!t || !b || !out || nb < 1 || nt < nb) return TOMATIS_E_ARG;
+  const i64 nc = nt - nb + 1;
+  const i64 groups = (nc + kOut - 1) / kOut;
+  if (groups > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k_al_xcorr, dim3((unsigned)groups), dim3(kT), 0, (hipStream_t)hs, t, (i64)nt,
+                     b, (i64)nb, out, nc);
+  return al_launch();
+}
+
+int tomatis_align_argmax(const float* c, int64_t n, int64_t* out_index, float* out_value,
+                         void* hs) {
+  if (!c || !out_index || !out_value || n < 1) return TOMATIS_E_ARG;
+  if (n > (int64_t)0xFFFFFFFF) return TOMATIS_E_UNSUPPORTED;  // 32-bit index in the key
+  hipStream_t s = (hipStream_t)hs;
+  const int rc = al_fail(hipMemsetAsync(out_index, 0, sizeof(int64_t), s));
+  if (rc != TOMATIS_OK) return rc;
+  const i64 want = (n + kT - 1) / kT, cap = (i64)al_cus() * 8;
+  hipLaunchKernelGGL(k_al_argmax, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, c,
+                     (i64)n, reinterpret_cast<u64*>(out_index));
+  hipLaunchKernelGGL(k_al_decode, dim3(1), dim3(1), 0, s, c, (i64*)out_index, out_value);
+  return al_launch();
+}
+
+}  // extern "C"
