@@ -649,6 +649,62 @@ int tomatis_align_xcorr(const float* t, int64_t nt, const float* b, int64_t nb, 
 int tomatis_align_argmax(const float* c, int64_t n, int64_t* out_index, float* out_value,
                          void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * compare_audio (src/compare_audio.py; tm_align.hip,
+ * tm_fftcorr.hip).  All buffers device-resident.
+ * ------------------------------------------------------------------------- */
+
+/* The envelope in compare_audio's order (compare_audio.py:7-10, :33-34): the
+ * mean is removed before the decimation.  e as in tomatis_align_envelope,
+ * mu = mean(e) over the range (float64 sums in a fixed order),
+ *   y[j] = sum_m taps[m] d[down j + (n_taps - 1) / 2 - m],  d = e - float32(mu)
+ * inside [0, len) and zero outside: resample_poly(e - e.mean(), 1, down).
+ * out[j] = y[j]; out_mean[0] = mu.  Arguments and limits as
+ * tomatis_align_envelope. */
+int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t start, int64_t len,
+                                      int32_t down, const float* taps, int32_t n_taps, float* out,
+                                      double* out_mean, void* hip_stream);
+
+/* log2 of the lengths tomatis_fft_pow2 takes */
+#define TOMATIS_FFT_MIN_LOG2 4
+#define TOMATIS_FFT_MAX_LOG2 25
+
+/* Bytes of workspace (8-byte aligned) of tomatis_fft_pow2 for 2^log2n points;
+ * 0 outside the supported range. */
+int64_t tomatis_fft_pow2_work_bytes(int32_t log2n);
+
+/* Complex float32 FFT of L = 2^log2n interleaved (re, im) points, what
+ * fftconvolve (compare_audio.py:37) runs underneath: out[k] = sum_n in[n]
+ * exp(-+2 pi i n k / L), the inverse (inverse != 0) with the 1 / L scale.  in and
+ * out are distinct buffers of L points.  Twiddles are float64 values rounded
+ * once; the same bits in every run.  TOMATIS_E_UNSUPPORTED outside
+ * [TOMATIS_FFT_MIN_LOG2, TOMATIS_FFT_MAX_LOG2]. */
+int tomatis_fft_pow2(const float* in, float* out, int32_t log2n, int32_t inverse, void* work,
+                     void* hip_stream);
+
+/* Bytes of workspace of tomatis_align_xcorr_full; 0 when nc + nb - 1 exceeds
+ * 2^TOMATIS_FFT_MAX_LOG2 (or a length is < 1). */
+int64_t tomatis_align_xcorr_full_work_bytes(int64_t nc, int64_t nb);
+
+/* out[k] = sum_j c[k - (nb - 1) + j] b[j], k < nc + nb - 1 (c zero outside
+ * [0, nc)): fftconvolve(c, b[::-1], mode="full") (compare_audio.py:37), as
+ * one forward transform of c + i b zero-padded to the next power of two
+ * L >= max(nc + nb - 1, 16), C conj(B), and the inverse transform.  nc + nb - 1 >
+ * 2^TOMATIS_FFT_MAX_LOG2: TOMATIS_E_UNSUPPORTED. */
+int tomatis_align_xcorr_full(const float* c, int64_t nc, const float* b, int64_t nb, float* out,
+                             void* work, void* hip_stream);
+
+/* doubles behind out of tomatis_compare_residual: [0], [1] the means, the
+ * rest scratch */
+#define TOMATIS_RESIDUAL_DOUBLES 2050
+
+/* The two means of compare_audio.py:96-99 over n frames of the interleaved
+ * stereo float32 b and c: out[0] = mean(power_mono(b)^2), out[1] =
+ * mean(power_mono(b - gain c)^2); float32 elementwise, float64 sums in a fixed
+ * order.  The host forms rms_db (:53-54) and the SNR from them. */
+int tomatis_compare_residual(const float* b, const float* c, int64_t n, float gain, double* out,
+                             void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ OPT_FUSE_LIMITER = 1     # TOMATIS_OPT_FUSE_LIMITER
 OPT_LIMITER_SPIN = 2     # TOMATIS_OPT_LIMITER_SPIN
 OPT_MINHOLD_SERIAL = 3   # TOMATIS_OPT_MINHOLD_SERIAL
 ALIGN_MEAN_DOUBLES = 1025  # TOMATIS_ALIGN_MEAN_DOUBLES
+RESIDUAL_DOUBLES = 2050    # TOMATIS_RESIDUAL_DOUBLES
+FFT_MIN_LOG2, FFT_MAX_LOG2 = 4, 25  # TOMATIS_FFT_MIN_LOG2, TOMATIS_FFT_MAX_LOG2
 # development overrides (TOMATIS_DEV_*: tests and A/B experiments only)
 DEV_KEYS = dict(FAST_LOOP=1, RUN_ROUNDS=2, RUN_FRAMES=3, LEVELS_LEGACY=4, GATE_TF=5, MH_PARTS=6,
                 FORCE_LDS=7, P64=8, ALPHA_SEQ=9, GAIN_LDS=10, FUSE_LIMITER=11, WG=12,
@@ -165,6 +167,14 @@ _SIGS = {
                                          C.c_int32, _P, _P, _P]),
     "tomatis_align_xcorr": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
     "tomatis_align_argmax": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    # compare_audio
+    "tomatis_align_envelope_mean_first": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64,
+                                                    C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "tomatis_fft_pow2_work_bytes": (C.c_int64, [C.c_int32]),
+    "tomatis_fft_pow2": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tomatis_align_xcorr_full_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "tomatis_align_xcorr_full": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    "tomatis_compare_residual": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -16,6 +16,17 @@ ratio, and a target whose envelope is shorter than the base chunk's (scipy's
 ``fftconvolve`` swaps its operands there), run the reference's scipy calls on
 the host (``_find_delay_host``).  Otherwise there is no CPU fallback.
 Inputs are numpy arrays, resident cuda tensors or file paths.
+
+compare_audio's estimate (src/compare_audio.py:30-42) is
+the "full" correlation of the two whole envelopes, the mean removed before the
+decimation:
+
+  ``resample_poly(m - m.mean(), ds_sr, sr)`` :33-34  tomatis_align_envelope_mean_first
+  fftconvolve(c, b[::-1], "full") :37                tomatis_align_xcorr_full (tm_fftcorr.hip)
+  np.argmax :38, the shift :39-42                    tomatis_align_argmax, host scalars
+
+``find_delay_full`` runs ``_find_delay_full_host`` (the reference's scipy body)
+for a ratio the decimator does not take and for nc + nb - 1 above 2^25.
 """
 from __future__ import annotations
 
@@ -25,10 +36,11 @@ import math
 import numpy as np
 
 from . import audio_io
-from ._lib import ALIGN_MEAN_DOUBLES, check, lib, ptr, stream_handle
+from ._lib import ALIGN_MEAN_DOUBLES, FFT_MAX_LOG2, FFT_MIN_LOG2, check, lib, ptr, stream_handle
 
 EPS = 1e-12
 MAX_DOWN = 64  # tm_align.hip kMaxDown
+MAX_FULL = 1 << FFT_MAX_LOG2  # lags of xcorr_full (tm_fftcorr.hip kMaxLog)
 
 
 def _torch():
@@ -78,9 +90,12 @@ def _vec_dev(a):
     return _stereo_dev(a).reshape(-1)
 
 
-def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False):
+def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False,
+                mean_first=False):
     """``m = resample_poly(power_mono(x_lr[start:stop]), ds_sr, sr).astype(float32);
-    m -= np.mean(m)`` as a cuda tensor (``with_mean``: and the mean removed)."""
+    m -= np.mean(m)`` as a cuda tensor (``with_mean``: and the mean removed).
+    ``mean_first``: compare_audio's order (:33-34), ``m = power_mono(...);
+    resample_poly(m - m.mean(), ds_sr, sr)``."""
     torch = _torch()
     if not device_ratio(sr, ds_sr):
         raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the device decimator takes sr % ds_sr == 0 "
@@ -99,8 +114,9 @@ def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False)
     taps = torch.from_numpy(_taps(down)).cuda()
     out = torch.empty(-(-ln // down), dtype=torch.float32, device="cuda")
     mean = torch.empty(ALIGN_MEAN_DOUBLES, dtype=torch.float64, device="cuda")
-    check(lib().tomatis_align_envelope(ptr(xd), n, start, ln, down, ptr(taps), taps.numel(),
-                                       ptr(out), ptr(mean), stream_handle()), "align_envelope")
+    fn = lib().tomatis_align_envelope_mean_first if mean_first else lib().tomatis_align_envelope
+    check(fn(ptr(xd), n, start, ln, down, ptr(taps), taps.numel(), ptr(out), ptr(mean),
+             stream_handle()), "align_envelope")
     return (out, float(mean[0].item())) if with_mean else out
 
 
@@ -114,6 +130,43 @@ def xcorr_valid(t, b):
     out = torch.empty(nt - nb + 1, dtype=torch.float32, device="cuda")
     check(lib().tomatis_align_xcorr(ptr(td), nt, ptr(bd), nb, ptr(out), stream_handle()),
           "align_xcorr")
+    return out
+
+
+def fft_pow2(x, inverse=False):
+    """``np.fft.fft`` / ``np.fft.ifft`` of a complex64 vector of 2^p points,
+    FFT_MIN_LOG2 <= p <= FFT_MAX_LOG2 (tomatis_fft_pow2): complex64 cuda tensor."""
+    torch = _torch()
+    if isinstance(x, torch.Tensor):
+        xd = x.to(device="cuda", dtype=torch.complex64).contiguous().reshape(-1)
+    else:
+        xd = torch.from_numpy(np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)).cuda()
+    n = xd.numel()
+    p = n.bit_length() - 1
+    if n < 1 or (1 << p) != n or not FFT_MIN_LOG2 <= p <= FFT_MAX_LOG2:
+        raise ValueError(f"fft_pow2 takes 2^{FFT_MIN_LOG2} .. 2^{FFT_MAX_LOG2} points, not {n}")
+    work = torch.empty(int(lib().tomatis_fft_pow2_work_bytes(p)), dtype=torch.uint8, device="cuda")
+    out = torch.empty_like(xd)
+    check(lib().tomatis_fft_pow2(ptr(xd), ptr(out), p, int(bool(inverse)), ptr(work),
+                                 stream_handle()), "fft_pow2")
+    return out
+
+
+def xcorr_full(c, b):
+    """``fftconvolve(c, b[::-1], mode="full")`` (compare_audio.py:37): cuda tensor
+    of len(c) + len(b) - 1 lags, out[k] = sum_j c[k - (len(b) - 1) + j] b[j]."""
+    torch = _torch()
+    cd, bd = _vec_dev(c), _vec_dev(b)
+    nc, nb = cd.numel(), bd.numel()
+    if nc < 1 or nb < 1:
+        raise ValueError("xcorr_full needs non-empty inputs")
+    if nc + nb - 1 > MAX_FULL:
+        raise ValueError(f"xcorr_full takes len(c) + len(b) - 1 <= {MAX_FULL}")
+    work = torch.empty(int(lib().tomatis_align_xcorr_full_work_bytes(nc, nb)), dtype=torch.uint8,
+                       device="cuda")
+    out = torch.empty(nc + nb - 1, dtype=torch.float32, device="cuda")
+    check(lib().tomatis_align_xcorr_full(ptr(cd), nc, ptr(bd), nb, ptr(out), ptr(work),
+                                         stream_handle()), "align_xcorr_full")
     return out
 
 
@@ -190,5 +243,46 @@ def find_delay(target, base, sr=48000, ds_sr=2000, chunk_sec=25):
     return _delay(k, mb_ds.numel(), s, e, sr, ds_sr)
 
 
-__all__ = ["envelope_ds", "xcorr_valid", "argmax_first", "find_delay", "device_ratio",
-           "power_mono"]
+def _delay_full(k: int, nb: int, sr: int, ds_sr: int) -> int:
+    """compare_audio.py:39-41."""
+    shift_ds = k - (nb - 1)
+    return int(round(shift_ds * (sr / ds_sr)))
+
+
+def _delay_full_host(base_mono, cand_mono, sr, ds_sr=2000):
+    """The reference's own scipy calls on the host (compare_audio.py:30-42) on
+    the two power-mono signals."""
+    from scipy.signal import fftconvolve, resample_poly
+    b = resample_poly(base_mono - base_mono.mean(), ds_sr, sr).astype(np.float32)
+    c = resample_poly(cand_mono - cand_mono.mean(), ds_sr, sr).astype(np.float32)
+    corr = fftconvolve(c, b[::-1], mode="full")
+    return _delay_full(int(np.argmax(corr)), len(b), sr, ds_sr)
+
+
+def _find_delay_full_host(base, cand, sr=48000, ds_sr=2000):
+    """``_delay_full_host`` of two stereo signals, for the cases the device path
+    leaves out."""
+    xb, _ = _load(base, sr)
+    xc, _ = _load(cand, sr)
+    return _delay_full_host(power_mono(_host(xb).astype(np.float32, copy=False)),
+                            power_mono(_host(xc).astype(np.float32, copy=False)), sr, ds_sr)
+
+
+def find_delay_full(base, cand, sr=48000, ds_sr=2000):
+    """delay = cand - base in samples from the full correlation of the whole
+    envelopes, compare_audio.find_delay_by_corr (:30-42)."""
+    xb, _ = _load(base, sr)
+    xc, _ = _load(cand, sr)
+    if not device_ratio(sr, ds_sr) or len(xb) < 1 or len(xc) < 1:
+        return _find_delay_full_host(xb, xc, sr, ds_sr)
+    _, down = _ratio(sr, ds_sr)
+    if -(-len(xb) // down) + -(-len(xc) // down) - 1 > MAX_FULL:
+        return _find_delay_full_host(xb, xc, sr, ds_sr)
+    b = envelope_ds(xb, sr, ds_sr, mean_first=True)
+    c = envelope_ds(xc, sr, ds_sr, mean_first=True)
+    k = argmax_first(xcorr_full(c, b))
+    return _delay_full(k, b.numel(), sr, ds_sr)
+
+
+__all__ = ["envelope_ds", "xcorr_valid", "fft_pow2", "xcorr_full", "argmax_first", "find_delay",
+           "find_delay_full", "device_ratio", "power_mono"]

@@ -1,6 +1,6 @@
 """Build ``libtomatis_hip.so`` in-tree with hipcc for gfx950 (no cmake/ninja needed).
 
-Seven translation units, compiled in parallel and linked into one C-ABI library:
+Eight translation units, compiled in parallel and linked into one C-ABI library:
 
 * ``tm_kernels.hip``   levels, gate, limiter, plan and the ``extern "C"`` entry points;
 * ``tm_transform.hip`` the fused transform kernels (FMA contraction on;
@@ -13,7 +13,9 @@ Seven translation units, compiled in parallel and linked into one C-ABI library:
 * ``tm_declick.hip``   the de-click stage: MAD click detector and linear
   inpainting (row f5; ``-ffp-contract=off`` like the gate unit: it is bit-exact);
 * ``tm_align.hip``     the delay estimate: power-mono envelope decimator,
-  direct cross-correlation, arg-max (row f6).
+  direct cross-correlation, arg-max (row f6), the residual means of row f7;
+* ``tm_fftcorr.hip``   the power-of-two FFT in global memory and the "full"
+  correlation built on it (row f7).
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ UNITS = {  # source -> extra flags
     "tm_flacdec.hip": [],
     "tm_declick.hip": [],
     "tm_align.hip": [],
+    "tm_fftcorr.hip": [],
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
                                         "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h")] + \

@@ -7,6 +7,10 @@
 //                                                           k_al_sum, k_al_center
 //   fftconvolve(mt_ds, mb_ds[::-1], "valid")             :47      -> k_al_xcorr
 //   np.argmax                                            :48      -> k_al_argmax, k_al_decode
+// and two pieces of src/compare_audio.py (row f7; its correlation is tm_fftcorr.hip):
+//   power_mono, resample_poly(m - m.mean(), 1, down)     :7-10,33-34 -> k_al_pm_sum, k_al_means,
+//                                                           k_al_envelope<., true>
+//   rms_db of power_mono(b) and of power_mono(b - g c)   :96-98   -> k_al_residual, k_al_means
 //
 // Layout (wave64, 256-thread workgroups):
 //  * envelope: a workgroup owns T consecutive outputs (T = blockDim.x).  It
@@ -77,11 +81,16 @@ __device__ __forceinline__ float power_mono(float l, float r) {
   return sqrtf(__fadd_rn(p, 1e-12f));
 }
 
-template <bool VEC>
+// SUB: e - float32(mu[0]) inside the range (compare_audio.py:33-34 removes the
+// mean before it decimates), still zero outside it
+template <bool VEC, bool SUB>
 __global__ __launch_bounds__(kT) void k_al_envelope(const float* __restrict__ x, i64 len, int down,
                                                      const float* __restrict__ taps, int n_taps,
-                                                     int Q, float* __restrict__ out, i64 n_out) {
+                                                     int Q, float* __restrict__ out, i64 n_out,
+                                                     const double* __restrict__ mu) {
   extern __shared__ float stage[];  // [down][Q]
+  float mf = 0.0f;
+  if constexpr (SUB) mf = (float)mu[0];
   const int T = blockDim.x, tid = threadIdx.x;
   const i64 j0 = (i64)blockIdx.x * T;
   const int half = (n_taps - 1) / 2;
@@ -97,6 +106,7 @@ __global__ __launch_bounds__(kT) void k_al_envelope(const float* __restrict__ x,
       } else {
         e = power_mono(x[2 * g], x[2 * g + 1]);
       }
+      if constexpr (SUB) e = __fsub_rn(e, mf);
     }
     const int q = i / down;
     stage[(i - q * down) * Q + q] = e;
@@ -144,6 +154,68 @@ __global__ __launch_bounds__(kT) void k_al_sum(const float* __restrict__ y, i64 
     s += (double)y[i];
   s = block_sum(s, sm);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// part[g] = float64 sum of power_mono(x[i]), i = g kT + t (mod G kT), G = gridDim.x
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_al_pm_sum(const float* __restrict__ x, i64 n,
+                                                   double* __restrict__ part) {
+  __shared__ double sm[kT / 64];
+  double s = 0.0;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT) {
+    if constexpr (VEC) {
+      const float2 v = *reinterpret_cast<const float2*>(x + 2 * i);
+      s += (double)power_mono(v.x, v.y);
+    } else {
+      s += (double)power_mono(x[2 * i], x[2 * i + 1]);
+    }
+  }
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// out[r] = sum(part[r * stride + i], i < n_part) / n, r < n_res: one workgroup
+__global__ __launch_bounds__(kT) void k_al_means(const double* __restrict__ part, int n_part,
+                                                  int stride, int n_res, i64 n,
+                                                  double* __restrict__ out) {
+  __shared__ double sm[kT / 64];
+  for (int r = 0; r < n_res; ++r) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += kT) s += part[r * stride + i];
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) out[r] = s / (double)n;
+  }
+}
+
+// compare_audio.py:96-99: part[g] = float64 sum of power_mono(b)^2, part[kSumGroups + g] of
+// power_mono(b - gain c)^2, squares in float32 as rms_db's x * x
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_al_residual(const float* __restrict__ b,
+                                                     const float* __restrict__ c, i64 n,
+                                                     float gain, double* __restrict__ part) {
+  __shared__ double sm[kT / 64];
+  double sb = 0.0, sr = 0.0;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT) {
+    float bl, br, cl, cr;
+    if constexpr (VEC) {
+      const float2 u = *reinterpret_cast<const float2*>(b + 2 * i);
+      const float2 v = *reinterpret_cast<const float2*>(c + 2 * i);
+      bl = u.x, br = u.y, cl = v.x, cr = v.y;
+    } else {
+      bl = b[2 * i], br = b[2 * i + 1], cl = c[2 * i], cr = c[2 * i + 1];
+    }
+    const float pb = power_mono(bl, br);
+    const float pr = power_mono(__fsub_rn(bl, __fmul_rn(gain, cl)),
+                                __fsub_rn(br, __fmul_rn(gain, cr)));
+    sb += (double)__fmul_rn(pb, pb);
+    sr += (double)__fmul_rn(pr, pr);
+  }
+  sb = block_sum(sb, sm);
+  sr = block_sum(sr, sm);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = sb;
+    part[kSumGroups + blockIdx.x] = sr;
+  }
 }
 
 // y -= float32(sum(part) / n); mean[0] = sum(part) / n
@@ -281,19 +353,9 @@ __global__ void k_al_decode(const float* __restrict__ c, i64* index, float* valu
 
 bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) == 0; }
 
-}  // namespace
-
-extern "C" {
-
-int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
-                           int32_t down, const float* taps, int32_t n_taps, float* out,
-                           double* out_mean, void* hs) {
-  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
-      len > n_total - start || down < 2 || n_taps < 1 || (n_taps & 1) == 0)
-    return TOMATIS_E_ARG;
-  if (down > kMaxDown || n_taps > 20 * down + 1) return TOMATIS_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)hs;
-  const i64 n_out = (len + down - 1) / down;
+// the decimator's launch; mu: the mean to remove first (mean-first order) or null
+int al_decimate(const float* xs, i64 len, int down, const float* taps, int n_taps, float* out,
+                i64 n_out, const double* mu, hipStream_t s) {
   // the largest of 256 / 128 / 64 outputs per workgroup whose staging fits
   int T = kT, Q = 0;
   for (;; T >>= 1) {
@@ -303,13 +365,76 @@ int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64
   const size_t lds = (size_t)down * Q * sizeof(float);
   const i64 groups = (n_out + T - 1) / T;
   if (groups > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
+  const bool vec = aligned(xs, 8);
+#define TM_AL_ENV(V, S)                                                                       \
+  hipLaunchKernelGGL((k_al_envelope<V, S>), dim3((unsigned)groups), dim3(T), lds, s, xs, len, \
+                     down, taps, n_taps, Q, out, n_out, mu)
+  if (mu) {
+    if (vec) TM_AL_ENV(true, true); else TM_AL_ENV(false, true);
+  } else {
+    if (vec) TM_AL_ENV(true, false); else TM_AL_ENV(false, false);
+  }
+#undef TM_AL_ENV
+  return TOMATIS_OK;
+}
+
+int al_env_args(const float* x, int64_t n_total, int64_t start, int64_t len, int32_t down,
+                const float* taps, int32_t n_taps, float* out, double* out_mean) {
+  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
+      len > n_total - start || down < 2 || n_taps < 1 || (n_taps & 1) == 0)
+    return TOMATIS_E_ARG;
+  if (down > kMaxDown || n_taps > 20 * down + 1) return TOMATIS_E_UNSUPPORTED;
+  return TOMATIS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t start, int64_t len,
+                                      int32_t down, const float* taps, int32_t n_taps, float* out,
+                                      double* out_mean, void* hs) {
+  int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
+  if (rc != TOMATIS_OK) return rc;
+  hipStream_t s = (hipStream_t)hs;
   const float* xs = x + 2 * start;
+  const i64 want = ((i64)len + kT - 1) / kT;
+  const int G = (int)(want < kSumGroups ? want : kSumGroups);
   if (aligned(xs, 8))
-    hipLaunchKernelGGL(k_al_envelope<true>, dim3((unsigned)groups), dim3(T), lds, s, xs, (i64)len,
-                       (int)down, taps, (int)n_taps, Q, out, n_out);
+    hipLaunchKernelGGL(k_al_pm_sum<true>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
   else
-    hipLaunchKernelGGL(k_al_envelope<false>, dim3((unsigned)groups), dim3(T), lds, s, xs,
-                       (i64)len, (int)down, taps, (int)n_taps, Q, out, n_out);
+    hipLaunchKernelGGL(k_al_pm_sum<false>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
+  hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out_mean + 1), G, 0, 1,
+                     (i64)len, out_mean);
+  rc = al_decimate(xs, (i64)len, (int)down, taps, (int)n_taps, out, ((i64)len + down - 1) / down,
+                   out_mean, s);
+  return rc != TOMATIS_OK ? rc : al_launch();
+}
+
+int tomatis_compare_residual(const float* b, const float* c, int64_t n, float gain, double* out,
+                             void* hs) {
+  if (!b || !c || !out || n < 1) return TOMATIS_E_ARG;
+  hipStream_t s = (hipStream_t)hs;
+  const i64 want = ((i64)n + kT - 1) / kT;
+  const int G = (int)(want < kSumGroups ? want : kSumGroups);
+  if (aligned(b, 8) && aligned(c, 8))
+    hipLaunchKernelGGL(k_al_residual<true>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 2);
+  else
+    hipLaunchKernelGGL(k_al_residual<false>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 2);
+  hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out + 2), G, kSumGroups,
+                     2, (i64)n, out);
+  return al_launch();
+}
+
+int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
+                           int32_t down, const float* taps, int32_t n_taps, float* out,
+                           double* out_mean, void* hs) {
+  int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
+  if (rc != TOMATIS_OK) return rc;
+  hipStream_t s = (hipStream_t)hs;
+  const i64 n_out = (len + down - 1) / down;
+  rc = al_decimate(x + 2 * start, (i64)len, (int)down, taps, (int)n_taps, out, n_out, nullptr, s);
+  if (rc != TOMATIS_OK) return rc;
   const i64 want = (n_out + kT - 1) / kT;
   const int G = (int)(want < kSumGroups ? want : kSumGroups);
   hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, out_mean + 1);
