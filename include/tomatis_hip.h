@@ -665,6 +665,28 @@ int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t s
                                       int32_t down, const float* taps, int32_t n_taps, float* out,
                                       double* out_mean, void* hip_stream);
 
+/* The envelope decimated by a rational ratio, scipy.signal.resample_poly(e, up,
+ * down) for 1 <= up < down, gcd(up, down) = 1 (44.1 kHz -> 2 kHz is 20 / 441,
+ * 192 kHz -> 2 kHz is 1 / 96).  channels == 2: x is interleaved stereo and
+ * e = power_mono as in tomatis_align_envelope; channels == 1: x is a float32
+ * vector used as given (the reference's 1-D power-mono argument).  Over the
+ * frames [start, start + len), zero outside them,
+ *   y[j] = sum_i taps[down j + (n_taps - 1) / 2 - up i] e[i],  j < ceil(len up / down),
+ * for taps = float32(firwin(20 down + 1, 1 / down, window=("kaiser", 5.0))) *
+ * float32(up).  mean_first == 0: out[j] = y[j] - float32(mean(y)) and
+ * out_mean[0] = mean(y), as tomatis_align_envelope; mean_first != 0: e is
+ * replaced by e - float32(mean(e)) inside the range, out[j] = y[j] and
+ * out_mean[0] = mean(e), as tomatis_align_envelope_mean_first.  Float64 sums in
+ * a fixed order, float32 FMA chains joined in a fixed order: the same bits in
+ * every run.  TOMATIS_E_ARG: a null pointer, a bad range, an even n_taps,
+ * up >= down, channels not 1 or 2; TOMATIS_E_UNSUPPORTED: down > 512, up > 64,
+ * n_taps > 20 down + 1; both before anything is read.  out: ceil(len up / down)
+ * floats; out_mean: TOMATIS_ALIGN_MEAN_DOUBLES doubles. */
+int tomatis_align_envelope_rational(const float* x, int64_t n_total, int64_t start, int64_t len,
+                                    int32_t channels, int32_t up, int32_t down,
+                                    const float* taps, int32_t n_taps, int32_t mean_first,
+                                    float* out, double* out_mean, void* hip_stream);
+
 /* log2 of the lengths tomatis_fft_pow2 takes */
 #define TOMATIS_FFT_MIN_LOG2 4
 #define TOMATIS_FFT_MAX_LOG2 25

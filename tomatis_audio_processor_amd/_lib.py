@@ -20,6 +20,7 @@ GATE_NONE = -536870912   # TOMATIS_GATE_NONE
 ERR_LIMITER_WAIT = 1     # TOMATIS_ERR_LIMITER_WAIT
 ERR_PAIR_BARRIER = 2     # TOMATIS_ERR_PAIR_BARRIER
 ERR_GATE_CARRY = 4       # TOMATIS_ERR_GATE_CARRY
+E_ARG = -1               # TOMATIS_E_ARG
 E_UNSUPPORTED = -2       # TOMATIS_E_UNSUPPORTED
 OPT_FUSE_LIMITER = 1     # TOMATIS_OPT_FUSE_LIMITER
 OPT_LIMITER_SPIN = 2     # TOMATIS_OPT_LIMITER_SPIN
@@ -170,6 +171,9 @@ _SIGS = {
     # compare_audio
     "tomatis_align_envelope_mean_first": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64,
                                                     C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "tomatis_align_envelope_rational": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                                  C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                                  _P, _P, _P]),
     "tomatis_fft_pow2_work_bytes": (C.c_int64, [C.c_int32]),
     "tomatis_fft_pow2": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "tomatis_align_xcorr_full_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

@@ -11,10 +11,16 @@ row f6): ``find_delay_by_corr`` of the reference's workflow scripts
   chunk bounds :23-27, centres and rounding       host (scalars)
   :49-52
 
-The device path takes ``sr % ds_sr == 0`` with a decimation of 2..64.  Another
-ratio, and a target whose envelope is shorter than the base chunk's (scipy's
-``fftconvolve`` swaps its operands there), run the reference's scipy calls on
-the host (``_find_delay_host``).  Otherwise there is no CPU fallback.
+The decimator comes in two kernels.  ``sr % ds_sr == 0`` with a decimation of
+2..64 (48 and 96 kHz; ``device_ratio``) runs tomatis_align_envelope as above.
+Every other ratio up / down with up < down <= 512 and up <= 64 after reduction
+(``rational_ratio``: 44.1 kHz is 20 / 441, 88.2 kHz 10 / 441, 176.4 kHz 5 / 441,
+192 kHz 1 / 96) runs tomatis_align_envelope_rational (``envelope_rs``), the
+polyphase form of resample_poly with the taps staged by phase.  What is left
+runs the reference's scipy calls on the host (``_find_delay_host``): up > down,
+a larger ratio, and a target whose envelope is shorter than the base chunk's
+(scipy's ``fftconvolve`` swaps its operands there).  So does a rational ratio
+on a machine without a ROCm device; the integer path has no CPU fallback.
 Inputs are numpy arrays, resident cuda tensors or file paths.
 
 compare_audio's estimate (src/compare_audio.py:30-42) is
@@ -25,8 +31,11 @@ decimation:
   fftconvolve(c, b[::-1], "full") :37                tomatis_align_xcorr_full (tm_fftcorr.hip)
   np.argmax :38, the shift :39-42                    tomatis_align_argmax, host scalars
 
-``find_delay_full`` runs ``_find_delay_full_host`` (the reference's scipy body)
-for a ratio the decimator does not take and for nc + nb - 1 above 2^25.
+``find_delay_full`` picks the decimator in the same way and runs
+``_find_delay_full_host`` (the reference's scipy body) for a ratio neither
+kernel takes and for nc + nb - 1 above 2^25.  ``delay_full_mono`` is the same
+estimate on the reference's own arguments, two 1-D power-mono vectors
+(``channels == 1`` of the rational entry point, which also takes up = 1).
 """
 from __future__ import annotations
 
@@ -41,6 +50,7 @@ from ._lib import ALIGN_MEAN_DOUBLES, FFT_MAX_LOG2, FFT_MIN_LOG2, check, lib, pt
 EPS = 1e-12
 MAX_DOWN = 64  # tm_align.hip kMaxDown
 MAX_FULL = 1 << FFT_MAX_LOG2  # lags of xcorr_full (tm_fftcorr.hip kMaxLog)
+MAX_DOWN_RS, MAX_UP_RS = 512, 64  # tm_align.hip kRatMaxDown, kRatMaxUp
 
 
 def _torch():
@@ -58,6 +68,35 @@ def _ratio(sr: int, ds_sr: int):
 def device_ratio(sr: int, ds_sr: int) -> bool:
     up, down = _ratio(sr, ds_sr)
     return up == 1 and 2 <= down <= MAX_DOWN
+
+
+def rational_ratio(sr: int, ds_sr: int) -> bool:
+    """The ratios tomatis_align_envelope_rational takes (up = 1 included)."""
+    up, down = _ratio(sr, ds_sr)
+    return 1 <= up < down <= MAX_DOWN_RS and up <= MAX_UP_RS
+
+
+def _has_device() -> bool:
+    try:
+        import torch
+    except ImportError:
+        return False
+    return torch.cuda.is_available()
+
+
+def _n_ds(n: int, up: int, down: int) -> int:
+    """len(resample_poly(e, up, down)) for len(e) = n."""
+    return -(-n * up // down)
+
+
+@functools.lru_cache(maxsize=8)
+def _taps_rational(up: int, down: int) -> np.ndarray:
+    """resample_poly's own filter for float32 input and up < down: the window
+    design rounded to float32, then scaled by up in float32."""
+    from scipy.signal import firwin
+    h = firwin(20 * down + 1, 1.0 / down, window=("kaiser", 5.0)).astype(np.float32)
+    h *= up
+    return h
 
 
 @functools.lru_cache(maxsize=8)
@@ -117,6 +156,48 @@ def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False,
     fn = lib().tomatis_align_envelope_mean_first if mean_first else lib().tomatis_align_envelope
     check(fn(ptr(xd), n, start, ln, down, ptr(taps), taps.numel(), ptr(out), ptr(mean),
              stream_handle()), "align_envelope")
+    return (out, float(mean[0].item())) if with_mean else out
+
+
+def _load_rs(a, sr):
+    """-> (array or cuda tensor, [n, 2] or 1-D, is_tensor)."""
+    if isinstance(a, str):
+        a, got = audio_io.read(a)
+        assert got == sr
+    is_tensor = not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+    if not is_tensor:
+        a = np.asarray(a)
+    assert a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 2)
+    return a, is_tensor
+
+
+def envelope_rs(x, sr=44100, ds_sr=2000, start=0, stop=None, with_mean=False, mean_first=False):
+    """``envelope_ds`` for the ratios of ``rational_ratio``: ``resample_poly(e[start:stop],
+    ds_sr, sr)`` with the mean removed after (``mean_first``: before) the
+    decimation, as a cuda tensor.  ``x`` is stereo ``[n, 2]`` (e = power_mono) or
+    a 1-D vector taken as e itself, in float32."""
+    torch = _torch()
+    if not rational_ratio(sr, ds_sr):
+        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the rational decimator takes up < down <= "
+                         f"{MAX_DOWN_RS} and up <= {MAX_UP_RS}")
+    up, down = _ratio(sr, ds_sr)
+    x, is_tensor = _load_rs(x, sr)
+    n, ch = x.shape[0], x.ndim
+    stop = n if stop is None else min(int(stop), n)
+    start = int(start)
+    if not 0 <= start < stop:
+        raise ValueError("envelope_rs needs a non-empty range inside the signal")
+    ln = stop - start
+    if not is_tensor:  # a host array: only the range is uploaded
+        x, n, start = x[start:stop], ln, 0
+    xd = _stereo_dev(x)
+    taps = torch.from_numpy(_taps_rational(up, down)).cuda()
+    out = torch.empty(_n_ds(ln, up, down), dtype=torch.float32, device="cuda")
+    mean = torch.empty(ALIGN_MEAN_DOUBLES, dtype=torch.float64, device="cuda")
+    check(lib().tomatis_align_envelope_rational(ptr(xd), n, start, ln, ch, up, down, ptr(taps),
+                                                taps.numel(), int(bool(mean_first)), ptr(out),
+                                                ptr(mean), stream_handle()),
+          "align_envelope_rational")
     return (out, float(mean[0].item())) if with_mean else out
 
 
@@ -226,19 +307,29 @@ def _find_delay_host(target, base, sr=48000, ds_sr=2000, chunk_sec=25):
     return _delay(k, len(mb_ds), s, e, sr, ds_sr)
 
 
+def _decimator(sr, ds_sr):
+    """``envelope_ds`` where it applies, else ``envelope_rs``, else None (the host)."""
+    if device_ratio(sr, ds_sr):
+        return envelope_ds
+    if rational_ratio(sr, ds_sr) and _has_device():
+        return envelope_rs
+    return None
+
+
 def find_delay(target, base, sr=48000, ds_sr=2000, chunk_sec=25):
     """delay = target - base in samples (positive: the target starts later),
     layer2_analyze_eq.find_delay_by_corr (:17-52)."""
     xt, _ = _load(target, sr)
     xb, _ = _load(base, sr)
     s, e = _chunk(len(xb), sr, chunk_sec)
-    if not device_ratio(sr, ds_sr):
+    env = _decimator(sr, ds_sr)
+    if env is None:
         return _find_delay_host(xt, xb, sr, ds_sr, chunk_sec)
-    _, down = _ratio(sr, ds_sr)
-    if e <= s or len(xt) < 1 or -(-len(xt) // down) < -(-(e - s) // down):
+    up, down = _ratio(sr, ds_sr)
+    if e <= s or len(xt) < 1 or _n_ds(len(xt), up, down) < _n_ds(e - s, up, down):
         return _find_delay_host(xt, xb, sr, ds_sr, chunk_sec)
-    mb_ds = envelope_ds(xb, sr, ds_sr, s, e)
-    mt_ds = envelope_ds(xt, sr, ds_sr)
+    mb_ds = env(xb, sr, ds_sr, s, e)
+    mt_ds = env(xt, sr, ds_sr)
     k = argmax_first(xcorr_valid(mt_ds, mb_ds))
     return _delay(k, mb_ds.numel(), s, e, sr, ds_sr)
 
@@ -273,16 +364,33 @@ def find_delay_full(base, cand, sr=48000, ds_sr=2000):
     envelopes, compare_audio.find_delay_by_corr (:30-42)."""
     xb, _ = _load(base, sr)
     xc, _ = _load(cand, sr)
-    if not device_ratio(sr, ds_sr) or len(xb) < 1 or len(xc) < 1:
+    env = _decimator(sr, ds_sr)
+    if env is None or len(xb) < 1 or len(xc) < 1:
         return _find_delay_full_host(xb, xc, sr, ds_sr)
-    _, down = _ratio(sr, ds_sr)
-    if -(-len(xb) // down) + -(-len(xc) // down) - 1 > MAX_FULL:
+    up, down = _ratio(sr, ds_sr)
+    if _n_ds(len(xb), up, down) + _n_ds(len(xc), up, down) - 1 > MAX_FULL:
         return _find_delay_full_host(xb, xc, sr, ds_sr)
-    b = envelope_ds(xb, sr, ds_sr, mean_first=True)
-    c = envelope_ds(xc, sr, ds_sr, mean_first=True)
+    b = env(xb, sr, ds_sr, mean_first=True)
+    c = env(xc, sr, ds_sr, mean_first=True)
     k = argmax_first(xcorr_full(c, b))
     return _delay_full(k, b.numel(), sr, ds_sr)
 
 
-__all__ = ["envelope_ds", "xcorr_valid", "fft_pow2", "xcorr_full", "argmax_first", "find_delay",
-           "find_delay_full", "device_ratio", "power_mono"]
+def delay_full_mono(base_mono, cand_mono, sr, ds_sr=2000):
+    """``find_delay_full`` on the reference's own arguments, two 1-D power-mono
+    vectors (arrays or resident tensors), taken as float32.  The host body for a
+    ratio the rational decimator does not take and above 2^25 lags."""
+    up, down = _ratio(sr, ds_sr)
+    nb, nc = len(base_mono), len(cand_mono)
+    if (not (rational_ratio(sr, ds_sr) and _has_device()) or nb < 1 or nc < 1
+            or _n_ds(nb, up, down) + _n_ds(nc, up, down) - 1 > MAX_FULL):
+        return _delay_full_host(_host(base_mono), _host(cand_mono), sr, ds_sr)
+    b = envelope_rs(base_mono, sr, ds_sr, mean_first=True)
+    c = envelope_rs(cand_mono, sr, ds_sr, mean_first=True)
+    k = argmax_first(xcorr_full(c, b))
+    return _delay_full(k, b.numel(), sr, ds_sr)
+
+
+__all__ = ["envelope_ds", "envelope_rs", "xcorr_valid", "fft_pow2", "xcorr_full", "argmax_first",
+           "find_delay", "find_delay_full", "delay_full_mono", "device_ratio", "rational_ratio",
+           "power_mono"]

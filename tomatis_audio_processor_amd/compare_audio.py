@@ -61,10 +61,11 @@ def band_energy(mag, freqs, f1, f2):
 def find_delay_by_corr(base, cand, sr, ds_sr=2000):
     """compare_audio.py:30-42.  ``base`` / ``cand`` are the stereo ``[n, 2]``
     signals (arrays, cuda tensors or paths): the device forms their power mono
-    itself.  The reference's 1-D power-mono arrays are taken too and run its
-    scipy body on the host."""
-    if isinstance(base, np.ndarray) and base.ndim == 1:
-        return align._delay_full_host(base, cand, sr, ds_sr)
+    itself.  The reference's 1-D power-mono vectors are taken too: they go to
+    the device as they are (``align.delay_full_mono``; its scipy body on the
+    host for a ratio the rational decimator does not take)."""
+    if not isinstance(base, str) and getattr(base, "ndim", 0) == 1:
+        return align.delay_full_mono(base, cand, sr, ds_sr)
     return align.find_delay_full(base, cand, sr=sr, ds_sr=ds_sr)
 
 

@@ -7,6 +7,8 @@
 //                                                           k_al_sum, k_al_center
 //   fftconvolve(mt_ds, mb_ds[::-1], "valid")             :47      -> k_al_xcorr
 //   np.argmax                                            :48      -> k_al_argmax, k_al_decode
+//   resample_poly(e, up, down), 1 <= up < down (44.1 kHz: 20 / 441, 192 kHz: 1 / 96), both
+//   mean orders, stereo or 1-D input                              -> k_al_envelope_rat
 // and two pieces of src/compare_audio.py (row f7; its correlation is tm_fftcorr.hip):
 //   power_mono, resample_poly(m - m.mean(), 1, down)     :7-10,33-34 -> k_al_pm_sum, k_al_means,
 //                                                           k_al_envelope<., true>
@@ -387,9 +389,266 @@ int al_env_args(const float* x, int64_t n_total, int64_t start, int64_t len, int
   return TOMATIS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// rational-ratio decimator: resample_poly(e, up, down), 1 <= up < down
+// ---------------------------------------------------------------------------
+// With c = down j + half, p = c mod up and ih = c / up, output j is
+//   y[j] = sum_v taps[p + up (K - 1 - v)] e[ih - (K - 1) + v],  v < K = ceil(n_taps / up)
+// (a tap index >= n_taps counts as a zero tap).  A workgroup of kT threads owns
+// T consecutive outputs, S = kT / T threads each: thread (o, si) = (tid % T,
+// tid / T) sums the terms v in [si C, (si + 1) C) of output j0 + o in four
+// chains joined pairwise (up > 1: by v mod 4; up == 1: by the place in a row
+// of down samples, k_al_envelope's order); the S partial sums are added in the
+// order of si.  T, S and C depend on (up, down, n_taps) alone, and a tile's
+// result does not depend on the workgroup that computes it: the workgroups
+// are resident and walk the tiles, so each builds its tap table once.
+//   stage: the W samples from g0 = ih(j0) - (K - 1) on; sample g0 + i at word
+//          i + pad (i / down).  pad = 1 for up == 1 and an even down: lane o
+//          then starts at o (down + 1), an odd stride over the 32 banks of a
+//          4-byte read, where o down would put the 32 lanes of a half wave on
+//          gcd(down, 32) times fewer banks (one bank at 192 kHz, down = 96).
+//          For up > 1 the starts floor((p0 + down o) / up) step by a fraction
+//          and a pad would break at another v in every lane; pad = 0, and the
+//          441 family (22.05, 44.1, 88.2 words per lane) reads 2-way
+//          conflicted (DESIGN.md §7f has the count per ratio).
+//   tab:   the taps by phase, tab[p Ks + v] = taps[p + up (K - 1 - v)]: a
+//          thread's taps are consecutive words.  up > 1 reads them four at a
+//          time; Ks / 4 is odd, so the rows of 16 phases start on 16 distinct
+//          16-byte slots of the 64 banks.  up == 1 has one row, every lane
+//          reads the same word (a broadcast).  Where that row would leave
+//          room for fewer than 64 outputs' samples (down above 150) the taps
+//          are read from global memory instead and tab is empty.
+//   red:   the kT partial sums.
+constexpr int kRatMaxDown = 512;
+constexpr int kRatMaxUp = 64;
+constexpr int kRatLdsBytes = 64 * 1024;
+
+struct RatPlan {
+  int up, down, n_taps, K, Ks, T, C, W, pad, stage_words, tab_words;
+};
+
+__device__ __forceinline__ float rat_join(float a0, float a1, float a2, float a3) {
+  return (a0 + a1) + (a2 + a3);
+}
+
+// up == 1, the terms v in [v, v1) row by row of down samples: tap v is h[v] (REV: h[-v]),
+// sample v lies at sp[v + pad (v / down)]
+template <bool REV>
+__device__ __forceinline__ float rat_rows(const float* __restrict__ h, const float* sp, int v,
+                                          int v1, int down, int pad) {
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+  while (v < v1) {
+    const int q = v / down;
+    const int ve = min(v1, (q + 1) * down);
+    const float* col = sp + q * pad;
+    for (; v + 4 <= ve; v += 4) {
+      a0 = fmaf(REV ? h[-v] : h[v], col[v], a0);
+      a1 = fmaf(REV ? h[-v - 1] : h[v + 1], col[v + 1], a1);
+      a2 = fmaf(REV ? h[-v - 2] : h[v + 2], col[v + 2], a2);
+      a3 = fmaf(REV ? h[-v - 3] : h[v + 3], col[v + 3], a3);
+    }
+    for (; v < ve; ++v) a0 = fmaf(REV ? h[-v] : h[v], col[v], a0);
+  }
+  return rat_join(a0, a1, a2, a3);
+}
+
+// TAPS: 0 up > 1, the phase table in LDS; 1 up == 1, taps from global memory;
+// 2 up == 1, the reversed taps in LDS
+template <bool VEC, bool SUB, bool MONO, int TAPS>
+__global__ __launch_bounds__(kT) void k_al_envelope_rat(const float* __restrict__ x, i64 len,
+                                                         const float* __restrict__ taps,
+                                                         RatPlan pl, float* __restrict__ out,
+                                                         i64 n_out, int tiles,
+                                                         const double* __restrict__ mu) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* stage = lds;
+  float* tab = lds + pl.stage_words;
+  float* red = tab + pl.tab_words;
+  float mf = 0.0f;
+  if constexpr (SUB) mf = (float)mu[0];
+  const int tid = threadIdx.x, T = pl.T, up = pl.up, down = pl.down, K = pl.K;
+  if constexpr (TAPS != 1) {  // once per workgroup; the first barrier of the loop publishes it
+    for (int i = tid; i < pl.tab_words; i += kT) {
+      const int p = i / pl.Ks, v = i - p * pl.Ks;
+      const int m = p + up * (K - 1 - v);
+      tab[i] = (v < K && m < pl.n_taps) ? taps[m] : 0.0f;
+    }
+  }
+  const int si = tid / T, o = tid - si * T;
+  const int v0 = si * pl.C, v1 = min(K, v0 + pl.C);
+  // a workgroup walks the tiles of T outputs blockIdx.x, blockIdx.x + gridDim.x, ...
+  for (i64 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const i64 j0 = (i64)tile * T;
+    const i64 c0 = (i64)down * j0 + (pl.n_taps - 1) / 2;
+    const i64 ih0 = c0 / up;
+    const int p0 = (int)(c0 - ih0 * up);
+    const i64 g0 = ih0 - (K - 1);
+    __syncthreads();  // the previous tile's reads of stage and red
+    for (int i0 = tid; i0 < pl.W; i0 += 4 * kT) {
+      float2 raw[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // four loads in flight, from addresses clamped into the range
+        i64 g = g0 + i0 + k * kT;
+        g = g < 0 ? 0 : (g < len ? g : len - 1);
+        if constexpr (MONO) raw[k] = make_float2(x[g], 0.0f);
+        else if constexpr (VEC) raw[k] = *reinterpret_cast<const float2*>(x + 2 * g);
+        else raw[k] = make_float2(x[2 * g], x[2 * g + 1]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * kT;
+        const i64 g = g0 + i;
+        float e = 0.0f;  // the sub-range is a signal of its own: zeros outside it
+        if (g >= 0 && g < len) {
+          if constexpr (MONO) e = raw[k].x; else e = power_mono(raw[k].x, raw[k].y);
+          if constexpr (SUB) e = __fsub_rn(e, mf);
+        }
+        if (i < pl.W) {
+          if constexpr (TAPS != 0) stage[i + pl.pad * (i / down)] = e; else stage[i] = e;
+        }
+      }
+    }
+    __syncthreads();
+    const i64 j = j0 + o;
+    float part = 0.0f;
+    if (j < n_out && v0 < v1) {
+      if constexpr (TAPS != 0) {
+        const float* sp = stage + o * (down + pl.pad);  // sample o down
+        if constexpr (TAPS == 1)
+          part = rat_rows<true>(taps + (pl.n_taps - 1), sp, v0, v1, down, pl.pad);
+        else
+          part = rat_rows<false>(tab, sp, v0, v1, down, pl.pad);
+      } else {
+        const int xo = p0 + down * o, ao = xo / up, p = xo - ao * up;
+        const float* sp = stage + ao;
+        const float* h = tab + p * pl.Ks;
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+        int v = v0;
+#pragma unroll 4
+        for (; v + 4 <= v1; v += 4) {
+          const float4 t = *reinterpret_cast<const float4*>(h + v);
+          a0 = fmaf(t.x, sp[v], a0);
+          a1 = fmaf(t.y, sp[v + 1], a1);
+          a2 = fmaf(t.z, sp[v + 2], a2);
+          a3 = fmaf(t.w, sp[v + 3], a3);
+        }
+        for (; v < v1; ++v) a0 = fmaf(h[v], sp[v], a0);
+        part = rat_join(a0, a1, a2, a3);
+      }
+    }
+    if (T == kT) {
+      if (j < n_out) out[j] = part;
+    } else {
+      red[tid] = part;  // [si][o]
+      __syncthreads();
+      if (tid < T && j < n_out) {
+        float s = red[o];
+        for (int k = 1; k < kT / T; ++k) s += red[k * T + o];
+        out[j] = s;
+      }
+    }
+  }
+}
+
+// the largest T = 256, 128, ... 1 outputs per workgroup whose staging fits beside the tap
+// table (lds_taps) or alone (up == 1 only)
+bool rat_plan_for(int up, int down, int n_taps, bool lds_taps, RatPlan* pl) {
+  pl->up = up, pl->down = down, pl->n_taps = n_taps;
+  pl->K = (n_taps + up - 1) / up;
+  pl->Ks = 4 * (((pl->K + 3) / 4) | 1);
+  pl->pad = (up == 1 && (down & 1) == 0) ? 1 : 0;
+  pl->tab_words = lds_taps ? up * pl->Ks : 0;
+  for (int T = kT;; T >>= 1) {
+    const int S = kT / T;
+    pl->T = T;
+    pl->C = ((pl->K + S - 1) / S + 3) / 4 * 4;
+    pl->W = (up - 1 + down * (T - 1)) / up + pl->K;
+    pl->stage_words = (pl->W + pl->pad * (pl->W / down + 1) + 3) / 4 * 4;
+    const size_t bytes = sizeof(float) * ((size_t)pl->stage_words + pl->tab_words + kT);
+    if (bytes <= (size_t)kRatLdsBytes) return true;
+    if (T == 1) return false;
+  }
+}
+
+bool rat_plan(int up, int down, int n_taps, RatPlan* pl) {
+  if (rat_plan_for(up, down, n_taps, true, pl) && (up > 1 || pl->T >= 64)) return true;
+  return up == 1 && rat_plan_for(up, down, n_taps, false, pl);
+}
+
+int al_decimate_rat(const float* xs, i64 len, bool mono, const float* taps, const RatPlan& pl,
+                    float* out, i64 n_out, const double* mu, hipStream_t s) {
+  const size_t lds = sizeof(float) * ((size_t)pl.stage_words + pl.tab_words + kT);
+  const i64 tiles = (n_out + pl.T - 1) / pl.T;
+  if (tiles > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
+  const i64 cap = (i64)al_cus() * 4;  // resident workgroups, each builds its phase table once
+  const unsigned groups = (unsigned)(tiles < cap ? tiles : cap);
+  const bool vec = !mono && aligned(xs, 8);
+#define TM_AL_RAT(V, S, M, U)                                                               \
+  hipLaunchKernelGGL((k_al_envelope_rat<V, S, M, U>), dim3(groups), dim3(kT), lds, s, xs, len, \
+                     taps, pl, out, n_out, (int)tiles, mu)
+#define TM_AL_RAT_U(V, S, M)                             \
+  do {                                                   \
+    if (pl.up > 1) TM_AL_RAT(V, S, M, 0);                \
+    else if (pl.tab_words == 0) TM_AL_RAT(V, S, M, 1);   \
+    else TM_AL_RAT(V, S, M, 2);                          \
+  } while (0)
+#define TM_AL_RAT_S(V, M) \
+  do { if (mu) TM_AL_RAT_U(V, true, M); else TM_AL_RAT_U(V, false, M); } while (0)
+  if (mono) TM_AL_RAT_S(false, true);
+  else if (vec) TM_AL_RAT_S(true, false);
+  else TM_AL_RAT_S(false, false);
+#undef TM_AL_RAT_S
+#undef TM_AL_RAT_U
+#undef TM_AL_RAT
+  return TOMATIS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tomatis_align_envelope_rational(const float* x, int64_t n_total, int64_t start, int64_t len,
+                                    int32_t channels, int32_t up, int32_t down,
+                                    const float* taps, int32_t n_taps, int32_t mean_first,
+                                    float* out, double* out_mean, void* hs) {
+  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
+      len > n_total - start || (channels != 1 && channels != 2) || up < 1 || up >= down ||
+      n_taps < 1 || (n_taps & 1) == 0)
+    return TOMATIS_E_ARG;
+  if (down > kRatMaxDown || up > kRatMaxUp || n_taps > 20 * down + 1 ||
+      len > (int64_t)1 << 55)
+    return TOMATIS_E_UNSUPPORTED;
+  RatPlan pl;
+  if (!rat_plan((int)up, (int)down, (int)n_taps, &pl)) return TOMATIS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hs;
+  const bool mono = channels == 1;
+  const float* xs = x + (i64)channels * start;
+  const i64 n_out = ((i64)len * up + down - 1) / down;
+  int rc;
+  if (mean_first) {
+    const i64 want = ((i64)len + kT - 1) / kT;
+    const int G = (int)(want < kSumGroups ? want : kSumGroups);
+    if (mono)
+      hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
+    else if (aligned(xs, 8))
+      hipLaunchKernelGGL(k_al_pm_sum<true>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
+    else
+      hipLaunchKernelGGL(k_al_pm_sum<false>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
+    hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out_mean + 1), G, 0, 1,
+                       (i64)len, out_mean);
+    rc = al_decimate_rat(xs, (i64)len, mono, taps, pl, out, n_out, out_mean, s);
+    return rc != TOMATIS_OK ? rc : al_launch();
+  }
+  rc = al_decimate_rat(xs, (i64)len, mono, taps, pl, out, n_out, nullptr, s);
+  if (rc != TOMATIS_OK) return rc;
+  const i64 want = (n_out + kT - 1) / kT;
+  const int G = (int)(want < kSumGroups ? want : kSumGroups);
+  hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, out_mean + 1);
+  const i64 cap = (i64)al_cus() * 8;
+  hipLaunchKernelGGL(k_al_center, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, out,
+                     n_out, (const double*)(out_mean + 1), G, out_mean);
+  return al_launch();
+}
 
 int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t start, int64_t len,
                                       int32_t down, const float* taps, int32_t n_taps, float* out,
