@@ -633,7 +633,9 @@ int tomatis_declick_inpaint(const float* x, float* y, int64_t n_frames, int32_t 
  * float32(firwin(20 down + 1, 1 / down, window=("kaiser", 5.0)));
  * out_mean[0] = mean(y) (float64 sums in a fixed order), out[j] = y[j] -
  * float32(mean).  2 <= down <= 64, n_taps odd and <= 20 down + 1; out: ceil(len /
- * down) floats; out_mean: TOMATIS_ALIGN_MEAN_DOUBLES doubles. */
+ * down) floats; out_mean: TOMATIS_ALIGN_MEAN_DOUBLES doubles.  A wrapper with
+ * these limits over the one decimating kernel: the result of
+ * tomatis_align_envelope_rational with channels 2, up 1, mean_first 0. */
 int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
                            int32_t down, const float* taps, int32_t n_taps, float* out,
                            double* out_mean, void* hip_stream);
@@ -660,14 +662,15 @@ int tomatis_align_argmax(const float* c, int64_t n, int64_t* out_index, float* o
  *   y[j] = sum_m taps[m] d[down j + (n_taps - 1) / 2 - m],  d = e - float32(mu)
  * inside [0, len) and zero outside: resample_poly(e - e.mean(), 1, down).
  * out[j] = y[j]; out_mean[0] = mu.  Arguments and limits as
- * tomatis_align_envelope. */
+ * tomatis_align_envelope; the same wrapper with mean_first 1. */
 int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t start, int64_t len,
                                       int32_t down, const float* taps, int32_t n_taps, float* out,
                                       double* out_mean, void* hip_stream);
 
 /* The envelope decimated by a rational ratio, scipy.signal.resample_poly(e, up,
  * down) for 1 <= up < down, gcd(up, down) = 1 (44.1 kHz -> 2 kHz is 20 / 441,
- * 192 kHz -> 2 kHz is 1 / 96).  channels == 2: x is interleaved stereo and
+ * 192 kHz -> 2 kHz is 1 / 96, 48 kHz -> 2 kHz is 1 / 24): the decimator behind
+ * all three envelope entry points.  channels == 2: x is interleaved stereo and
  * e = power_mono as in tomatis_align_envelope; channels == 1: x is a float32
  * vector used as given (the reference's 1-D power-mono argument).  Over the
  * frames [start, start + len), zero outside them,

@@ -1,5 +1,5 @@
 """Plain numpy statement of the rational-ratio decimator (tm_align.hip
-k_al_envelope_rat): what ``scipy.signal.resample_poly(e, up, down)`` computes
+k_al_envelope): what ``scipy.signal.resample_poly(e, up, down)`` computes
 for up < down, written out term by term, and the inputs of the rational delay
 goldens (tests/golden/rational_cases.py), built once per process."""
 from __future__ import annotations

@@ -24,6 +24,7 @@ from scipy.signal import fftconvolve
 
 from tests import align_ref as ar
 from tests.golden.align_cases import DELAY_CASES, SR, make_pair
+from tests.golden.envelope_bits_cases import BITS_CASES, FIXTURE, make_input, run_entry_point
 from tests.stft_ref import white
 
 pytestmark = pytest.mark.gpu
@@ -47,11 +48,12 @@ def _rel(y, y64):
 # envelope
 # ---------------------------------------------------------------------------
 
-def _judge_envelope(al, x, down, start, stop, name):
+def _judge_envelope(al, x, down, start, stop, name, ds_sr=None):
     """x[start:stop] through the device against resample_poly; the whole x is
-    resident, so the samples around the range are live."""
+    resident, so the samples around the range are live.  ``ds_sr``: for a
+    ``down`` that does not divide 48000."""
     import torch
-    sr, ds_sr = 48000, 48000 // down
+    sr, ds_sr = (48000, 48000 // down) if ds_sr is None else (down * ds_sr, ds_sr)
     seg = x[start:stop]
     y64, mean64 = ar.envelope(seg, sr, ds_sr, np.float64)     # centred, and its mean
     peak = float(np.max(np.abs(y64 + mean64)))                # of the decimator's output
@@ -90,6 +92,64 @@ def test_envelope_rejects_other_ratios(al):
         al.envelope_ds(x, 44100, 2000)
     with pytest.raises(ValueError):
         al.envelope_ds(x, 48000, 500)   # decimation 96 > 64
+
+
+@functools.lru_cache(maxsize=None)
+def _bits_fixture():
+    return ar.fixture(FIXTURE)
+
+
+@pytest.mark.parametrize("case", BITS_CASES, ids=[c["key"] for c in BITS_CASES])
+def test_envelope_ds_bits_are_the_parent_commits(al, case):
+    """One decimating kernel serves every entry point.  Up to down = 53 it gives
+    one thread per output and sums in the order of the integer decimator it
+    replaced: the bits and the mean that decimator's library wrote
+    (tools/make_envelope_bits_goldens.py), from the C entry point and from
+    ``envelope_ds``."""
+    import torch
+    fx = _bits_fixture()
+    key = case["key"]
+    x, crc = make_input(case)
+    assert crc == int(fx[key + "_crc"]), \
+        f"{key}: the input differs from the fixture's (CRC {crc:08x}, not " \
+        f"{int(fx[key + '_crc']):08x}): numpy's generator changed, not the kernel"
+    bits, mean = run_entry_point(case, x)
+    assert np.array_equal(bits, fx[key + "_bits"]), key
+    assert mean == float(fx[key + "_mean"]), key
+    down = case["down"]
+    got, mean = al.envelope_ds(torch.from_numpy(x).cuda(), 1000 * down, 1000, case["start"],
+                               case["stop"], with_mean=True, mean_first=case["mean_first"])
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), fx[key + "_bits"]), key
+    assert mean == float(fx[key + "_mean"]), key
+
+
+@pytest.mark.parametrize("mean_first", [False, True], ids=["mean-last", "mean-first"])
+@pytest.mark.parametrize("per_down,plus", [(0, 1), (0, 65), (600, 17)])
+@pytest.mark.parametrize("down", [54, 64])
+def test_envelope_two_threads_per_output(al, down, per_down, plus, mean_first):
+    """down 54..64: the staging of 256 outputs no longer fits the LDS, a
+    workgroup owns 128 outputs with two threads each and the two partial sums
+    are added last, so these are not the integer decimator's bits; the bound
+    against float64 is the same.  Measured e / max(e32, 2^-23) on the MI355X
+    (profiles/align/gpu_tests_one_decimator.log), mean-last / mean-first:
+    down 54: 0.53 / 0.87 at 65 frames, 0.13 / 0.28 at 32 417;
+    down 64: 0.81 / 1.12 at 65 frames, 0.13 / 0.37 at 38 417; 0.00 at one frame.
+
+    One frame in mean-first order is exact zeros in every precision (the sample
+    less its own mean), which leaves the judge no scale to divide by: zeros and
+    the mean are asserted instead."""
+    from tests.test_gpu_compare import _judge_mean_first
+    n = per_down * down + plus
+    x = white(2300 + n % 1000 + down, n, 2)
+    name = f"len {n} down {down}"
+    if not mean_first:
+        _judge_envelope(al, x, down, 0, n, name, ds_sr=1000)
+    elif n > 1:
+        _judge_mean_first(al, x, down, 0, n, name, ds_sr=1000)
+    else:
+        got, mean = al.envelope_ds(x, 1000 * down, 1000, with_mean=True, mean_first=True)
+        assert got.shape == (1,) and not np.any(got.cpu().numpy())
+        assert mean == float(ar.power_mono(x)[0])
 
 
 # ---------------------------------------------------------------------------

@@ -193,9 +193,9 @@ def test_xcorr_full_over_the_cap(al):
 # the mean-first envelope
 # ---------------------------------------------------------------------------
 
-def _judge_mean_first(al, x, down, start, stop, name):
+def _judge_mean_first(al, x, down, start, stop, name, ds_sr=None):
     import torch
-    sr, ds_sr = 48000, 48000 // down
+    sr, ds_sr = (48000, 48000 // down) if ds_sr is None else (down * ds_sr, ds_sr)
     seg = x[start:stop]
     y64, mean64 = cr.envelope_mean_first(seg, sr, ds_sr, np.float64)
     y32, _ = cr.envelope_mean_first(seg, sr, ds_sr, np.float32)

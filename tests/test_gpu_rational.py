@@ -1,4 +1,4 @@
-"""GPU: the rational-ratio decimator (tm_align.hip k_al_envelope_rat behind
+"""GPU: the decimator at rational ratios (tm_align.hip k_al_envelope behind
 ``tomatis_align_envelope_rational``) on its own, and ``align.find_delay`` /
 ``find_delay_full`` / ``compare_audio.find_delay_by_corr`` at 44.1, 88.2 and
 192 kHz against the reference's goldens (tools/make_rational_goldens.py).
@@ -20,7 +20,8 @@ outputs_per_workgroup``), and 5 s + 17 samples at 44.1 kHz (10 001 outputs,
 
 Largest measured e / max(e32, 2^-23) on the MI355X: 1.48 (2 / 511 mean-first,
 512 samples), 1.41 (1 / 96 mean-first, 97 samples); 0.73 at 20 / 441; 0.27 at
-220 517 samples.  1 / 24 returns the bits of ``envelope_ds``.
+220 517 samples.  1 / 24 returns the bits of ``envelope_ds``: the same kernel
+behind another range check (tests/test_gpu_align.py pins those bits).
 """
 import ctypes as C
 
@@ -139,9 +140,10 @@ def test_envelope_against_float64(al, up, down, n, mean_first):
 
 @pytest.mark.parametrize("mean_first", [False, True], ids=["mean-last", "mean-first"])
 def test_integer_ratio_agrees_with_the_integer_decimator(al, mean_first):
-    """1 / 24 is legal through the new entry point too: the same bound against
-    float64, and the same bound on its distance from ``envelope_ds`` (another
-    summation order, so not the same bits)."""
+    """1 / 24 is legal through ``envelope_rs`` too: the same bound against
+    float64, and the bits of ``envelope_ds``, which is the same kernel behind
+    another range check (one summation order; tests/test_gpu_align.py holds it
+    to the bits of the integer decimator it replaced)."""
     n = 5 * 48000 + 17
     x = white(9200, n, 2)
     got = _judge(al, x, 1, 24, 0, n, mean_first, f"len {n}")
@@ -161,6 +163,7 @@ def test_integer_ratio_agrees_with_the_integer_decimator(al, mean_first):
     print(f"RATIO [envelope_rs 1/24 against envelope_ds]: d {d:.3e} e32 {e32:.3e} "
           f"ratio {d / max(e32, ar.FLOOR):.2f}")
     assert d <= ar.bound(e32), (d, e32)
+    assert np.array_equal(got.view(np.uint32), old.view(np.uint32))
 
 
 @pytest.mark.parametrize("up,down", [(20, 441), (1, 96)])

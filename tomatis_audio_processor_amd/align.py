@@ -11,16 +11,19 @@ row f6): ``find_delay_by_corr`` of the reference's workflow scripts
   chunk bounds :23-27, centres and rounding       host (scalars)
   :49-52
 
-The decimator comes in two kernels.  ``sr % ds_sr == 0`` with a decimation of
-2..64 (48 and 96 kHz; ``device_ratio``) runs tomatis_align_envelope as above.
-Every other ratio up / down with up < down <= 512 and up <= 64 after reduction
-(``rational_ratio``: 44.1 kHz is 20 / 441, 88.2 kHz 10 / 441, 176.4 kHz 5 / 441,
-192 kHz 1 / 96) runs tomatis_align_envelope_rational (``envelope_rs``), the
-polyphase form of resample_poly with the taps staged by phase.  What is left
-runs the reference's scipy calls on the host (``_find_delay_host``): up > down,
-a larger ratio, and a target whose envelope is shorter than the base chunk's
-(scipy's ``fftconvolve`` swaps its operands there).  So does a rational ratio
-on a machine without a ROCm device; the integer path has no CPU fallback.
+There is one decimating kernel, the polyphase form of resample_poly with the
+taps staged by phase, and ``envelope_ds`` and ``envelope_rs`` are two range
+checks in front of one body that calls tomatis_align_envelope_rational (the
+library's tomatis_align_envelope[_mean_first] are that call with two channels
+and up = 1).  ``envelope_ds`` takes ``sr % ds_sr == 0`` with a decimation of
+2..64 (48 and 96 kHz; ``device_ratio``), ``envelope_rs`` every ratio up / down
+with up < down <= 512 and up <= 64 after reduction (``rational_ratio``:
+44.1 kHz is 20 / 441, 88.2 kHz 10 / 441, 176.4 kHz 5 / 441, 192 kHz 1 / 96).
+What is left runs the reference's scipy calls on the host
+(``_find_delay_host``): up > down, a larger ratio, and a target whose envelope
+is shorter than the base chunk's (scipy's ``fftconvolve`` swaps its operands
+there).  So does a ratio of ``rational_ratio`` alone on a machine without a
+ROCm device; a ratio of ``device_ratio`` has no CPU fallback and raises there.
 Inputs are numpy arrays, resident cuda tensors or file paths.
 
 compare_audio's estimate (src/compare_audio.py:30-42) is
@@ -31,9 +34,9 @@ decimation:
   fftconvolve(c, b[::-1], "full") :37                tomatis_align_xcorr_full (tm_fftcorr.hip)
   np.argmax :38, the shift :39-42                    tomatis_align_argmax, host scalars
 
-``find_delay_full`` picks the decimator in the same way and runs
-``_find_delay_full_host`` (the reference's scipy body) for a ratio neither
-kernel takes and for nc + nb - 1 above 2^25.  ``delay_full_mono`` is the same
+``find_delay_full`` picks the range check in the same way and runs
+``_find_delay_full_host`` (the reference's scipy body) for a ratio the kernel
+does not take and for nc + nb - 1 above 2^25.  ``delay_full_mono`` is the same
 estimate on the reference's own arguments, two 1-D power-mono vectors
 (``channels == 1`` of the rational entry point, which also takes up = 1).
 """
@@ -99,22 +102,21 @@ def _taps_rational(up: int, down: int) -> np.ndarray:
     return h
 
 
-@functools.lru_cache(maxsize=8)
 def _taps(down: int) -> np.ndarray:
     """resample_poly's own filter for up = 1 and float32 input."""
-    from scipy.signal import firwin
-    return firwin(20 * down + 1, 1.0 / down, window=("kaiser", 5.0)).astype(np.float32)
+    return _taps_rational(1, down)
 
 
-def _load(a, sr):
-    """-> (array or cuda tensor [n, 2], is_tensor); the reference's asserts."""
+def _load(a, sr, mono_ok=False):
+    """-> (array or cuda tensor [n, 2], or 1-D where ``mono_ok``; is_tensor); the
+    reference's asserts."""
     if isinstance(a, str):
         a, got = audio_io.read(a)
         assert got == sr
     is_tensor = not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
     if not is_tensor:
         a = np.asarray(a)
-    assert a.ndim == 2 and a.shape[1] == 2
+    assert (mono_ok and a.ndim == 1) or (a.ndim == 2 and a.shape[1] == 2)
     return a, is_tensor
 
 
@@ -129,64 +131,17 @@ def _vec_dev(a):
     return _stereo_dev(a).reshape(-1)
 
 
-def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False,
-                mean_first=False):
-    """``m = resample_poly(power_mono(x_lr[start:stop]), ds_sr, sr).astype(float32);
-    m -= np.mean(m)`` as a cuda tensor (``with_mean``: and the mean removed).
-    ``mean_first``: compare_audio's order (:33-34), ``m = power_mono(...);
-    resample_poly(m - m.mean(), ds_sr, sr)``."""
+def _envelope(who, x, sr, ds_sr, start, stop, with_mean, mean_first, mono_ok):
+    """The body of ``envelope_ds`` and ``envelope_rs`` once the ratio is checked:
+    upload, allocate, one call of tomatis_align_envelope_rational."""
     torch = _torch()
-    if not device_ratio(sr, ds_sr):
-        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the device decimator takes sr % ds_sr == 0 "
-                         f"and a factor of 2..{MAX_DOWN}")
-    _, down = _ratio(sr, ds_sr)
-    x, is_tensor = _load(x_lr, sr)
-    n = x.shape[0]
-    stop = n if stop is None else min(int(stop), n)
-    start = int(start)
-    if not 0 <= start < stop:
-        raise ValueError("envelope_ds needs a non-empty range inside the signal")
-    ln = stop - start
-    if not is_tensor:  # a host array: only the range is uploaded
-        x, n, start = x[start:stop], ln, 0
-    xd = _stereo_dev(x)
-    taps = torch.from_numpy(_taps(down)).cuda()
-    out = torch.empty(-(-ln // down), dtype=torch.float32, device="cuda")
-    mean = torch.empty(ALIGN_MEAN_DOUBLES, dtype=torch.float64, device="cuda")
-    fn = lib().tomatis_align_envelope_mean_first if mean_first else lib().tomatis_align_envelope
-    check(fn(ptr(xd), n, start, ln, down, ptr(taps), taps.numel(), ptr(out), ptr(mean),
-             stream_handle()), "align_envelope")
-    return (out, float(mean[0].item())) if with_mean else out
-
-
-def _load_rs(a, sr):
-    """-> (array or cuda tensor, [n, 2] or 1-D, is_tensor)."""
-    if isinstance(a, str):
-        a, got = audio_io.read(a)
-        assert got == sr
-    is_tensor = not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
-    if not is_tensor:
-        a = np.asarray(a)
-    assert a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 2)
-    return a, is_tensor
-
-
-def envelope_rs(x, sr=44100, ds_sr=2000, start=0, stop=None, with_mean=False, mean_first=False):
-    """``envelope_ds`` for the ratios of ``rational_ratio``: ``resample_poly(e[start:stop],
-    ds_sr, sr)`` with the mean removed after (``mean_first``: before) the
-    decimation, as a cuda tensor.  ``x`` is stereo ``[n, 2]`` (e = power_mono) or
-    a 1-D vector taken as e itself, in float32."""
-    torch = _torch()
-    if not rational_ratio(sr, ds_sr):
-        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the rational decimator takes up < down <= "
-                         f"{MAX_DOWN_RS} and up <= {MAX_UP_RS}")
     up, down = _ratio(sr, ds_sr)
-    x, is_tensor = _load_rs(x, sr)
+    x, is_tensor = _load(x, sr, mono_ok)
     n, ch = x.shape[0], x.ndim
     stop = n if stop is None else min(int(stop), n)
     start = int(start)
     if not 0 <= start < stop:
-        raise ValueError("envelope_rs needs a non-empty range inside the signal")
+        raise ValueError(f"{who} needs a non-empty range inside the signal")
     ln = stop - start
     if not is_tensor:  # a host array: only the range is uploaded
         x, n, start = x[start:stop], ln, 0
@@ -199,6 +154,31 @@ def envelope_rs(x, sr=44100, ds_sr=2000, start=0, stop=None, with_mean=False, me
                                                 ptr(mean), stream_handle()),
           "align_envelope_rational")
     return (out, float(mean[0].item())) if with_mean else out
+
+
+def envelope_ds(x_lr, sr=48000, ds_sr=2000, start=0, stop=None, with_mean=False,
+                mean_first=False):
+    """``m = resample_poly(power_mono(x_lr[start:stop]), ds_sr, sr).astype(float32);
+    m -= np.mean(m)`` as a cuda tensor (``with_mean``: and the mean removed).
+    ``mean_first``: compare_audio's order (:33-34), ``m = power_mono(...);
+    resample_poly(m - m.mean(), ds_sr, sr)``."""
+    _torch()
+    if not device_ratio(sr, ds_sr):
+        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the device decimator takes sr % ds_sr == 0 "
+                         f"and a factor of 2..{MAX_DOWN}")
+    return _envelope("envelope_ds", x_lr, sr, ds_sr, start, stop, with_mean, mean_first, False)
+
+
+def envelope_rs(x, sr=44100, ds_sr=2000, start=0, stop=None, with_mean=False, mean_first=False):
+    """``envelope_ds`` for the ratios of ``rational_ratio``: ``resample_poly(e[start:stop],
+    ds_sr, sr)`` with the mean removed after (``mean_first``: before) the
+    decimation, as a cuda tensor.  ``x`` is stereo ``[n, 2]`` (e = power_mono) or
+    a 1-D vector taken as e itself, in float32."""
+    _torch()
+    if not rational_ratio(sr, ds_sr):
+        raise ValueError(f"sr={sr}, ds_sr={ds_sr}: the rational decimator takes up < down <= "
+                         f"{MAX_DOWN_RS} and up <= {MAX_UP_RS}")
+    return _envelope("envelope_rs", x, sr, ds_sr, start, stop, with_mean, mean_first, True)
 
 
 def xcorr_valid(t, b):

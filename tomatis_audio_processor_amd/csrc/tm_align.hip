@@ -3,26 +3,22 @@
 // find_delay_by_corr of the reference's workflow scripts
 // (src/layer2_analyze_eq.py:17-52, src/calibrate_to_baseline_v2.py:46-82) as
 // three kernel groups, each behind its own entry point:
-//   power_mono + resample_poly(e, 1, down) + "-= mean"   :31-33,43-45 -> k_al_envelope,
+//   power_mono + resample_poly(e, up, down) + "-= mean"  :31-33,43-45 -> k_al_envelope,
 //                                                           k_al_sum, k_al_center
 //   fftconvolve(mt_ds, mb_ds[::-1], "valid")             :47      -> k_al_xcorr
 //   np.argmax                                            :48      -> k_al_argmax, k_al_decode
-//   resample_poly(e, up, down), 1 <= up < down (44.1 kHz: 20 / 441, 192 kHz: 1 / 96), both
-//   mean orders, stereo or 1-D input                              -> k_al_envelope_rat
 // and two pieces of src/compare_audio.py (row f7; its correlation is tm_fftcorr.hip):
-//   power_mono, resample_poly(m - m.mean(), 1, down)     :7-10,33-34 -> k_al_pm_sum, k_al_means,
-//                                                           k_al_envelope<., true>
+//   power_mono, resample_poly(m - m.mean(), up, down)    :7-10,33-34 -> k_al_pm_sum, k_al_means,
+//                                                           k_al_envelope<., true, ., .>
 //   rms_db of power_mono(b) and of power_mono(b - g c)   :96-98   -> k_al_residual, k_al_means
+// One kernel decimates, for every ratio 1 <= up < down (48 kHz: 1 / 24, 44.1 kHz: 20 / 441,
+// 192 kHz: 1 / 96), both mean orders, stereo or 1-D input.  al_envelope launches it with
+// the sums of either order, and the three envelope entry points are argument checks in
+// front of al_envelope: tomatis_align_envelope[_mean_first] pass channels = 2 and up = 1.
 //
 // Layout (wave64, 256-thread workgroups):
-//  * envelope: a workgroup owns T consecutive outputs (T = blockDim.x).  It
-//    stages the down (T - 1) + n_taps envelope samples they read, formed from
-//    8-byte stereo loads (the PCM is read once; the halo of neighbouring
-//    workgroups comes from L2), in LDS as [phase][Q]: sample g0 + i lies at
-//    (i % down) * Q + i / down.  Tap u of output j then reads phase u % down at
-//    column j + u / down: consecutive lanes read consecutive words (no bank
-//    conflict), the tap itself is uniform (a scalar load).  Q is odd, so the
-//    staging stores of consecutive samples (stride Q) spread over the banks.
+//  * envelope: polyphase, a resident grid over tiles of T outputs with the
+//    samples and the taps of a tile in LDS; described at k_al_envelope.
 //  * mean: a fixed grid of at most kSumGroups workgroups writes float64
 //    partial sums (grid-stride, fixed order), every workgroup of the centring
 //    pass adds them up in index order: the same mean in every workgroup and in
@@ -55,7 +51,6 @@ typedef unsigned long long u64;
 constexpr int kT = 256;                   // threads per workgroup
 constexpr int kSumGroups = TOMATIS_ALIGN_MEAN_DOUBLES - 1;  // partial sums of the mean
 constexpr int kMaxDown = 64;
-constexpr int kLdsBytes = 48 * 1024;      // envelope staging budget
 constexpr int kR = 16;                    // outputs per lane of the correlation
 constexpr int kOut = kT * kR;             // outputs per workgroup
 constexpr int kJB = 1024;                 // template block staged in LDS
@@ -75,65 +70,18 @@ int al_cus() {
   return cus;
 }
 
+// workgroups of a fixed-order float64 sum over n items: min(ceil(n / kT), kSumGroups)
+int sum_groups(i64 n) {
+  const i64 want = (n + kT - 1) / kT;
+  return (int)(want < kSumGroups ? want : kSumGroups);
+}
+
 // ---------------------------------------------------------------------------
-// envelope: e = sqrt(0.5 (l l + r r) + 1e-12) in float32, decimating FIR
+// envelope: e = sqrt(0.5 (l l + r r) + 1e-12) in float32, and the sums behind its mean
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float power_mono(float l, float r) {
   const float p = __fmul_rn(0.5f, __fadd_rn(__fmul_rn(l, l), __fmul_rn(r, r)));
   return sqrtf(__fadd_rn(p, 1e-12f));
-}
-
-// SUB: e - float32(mu[0]) inside the range (compare_audio.py:33-34 removes the
-// mean before it decimates), still zero outside it
-template <bool VEC, bool SUB>
-__global__ __launch_bounds__(kT) void k_al_envelope(const float* __restrict__ x, i64 len, int down,
-                                                     const float* __restrict__ taps, int n_taps,
-                                                     int Q, float* __restrict__ out, i64 n_out,
-                                                     const double* __restrict__ mu) {
-  extern __shared__ float stage[];  // [down][Q]
-  float mf = 0.0f;
-  if constexpr (SUB) mf = (float)mu[0];
-  const int T = blockDim.x, tid = threadIdx.x;
-  const i64 j0 = (i64)blockIdx.x * T;
-  const int half = (n_taps - 1) / 2;
-  const i64 g0 = (i64)down * j0 - half;
-  const int cnt = down * (T - 1) + n_taps;
-  for (int i = tid; i < cnt; i += T) {
-    const i64 g = g0 + i;
-    float e = 0.0f;  // the sub-range is a signal of its own: zeros outside it
-    if (g >= 0 && g < len) {
-      if constexpr (VEC) {
-        const float2 v = *reinterpret_cast<const float2*>(x + 2 * g);
-        e = power_mono(v.x, v.y);
-      } else {
-        e = power_mono(x[2 * g], x[2 * g + 1]);
-      }
-      if constexpr (SUB) e = __fsub_rn(e, mf);
-    }
-    const int q = i / down;
-    stage[(i - q * down) * Q + q] = e;
-  }
-  __syncthreads();
-  const i64 j = j0 + tid;
-  if (j >= n_out) return;
-  // y[j] = sum_u taps[n_taps - 1 - u] e[down j - half + u], u = q down + p
-  const float* tp = taps + (n_taps - 1);
-  const int rows = n_taps / down, rem = n_taps - rows * down;
-  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;  // four chains, joined pairwise
-  for (int q = 0; q <= rows; ++q) {
-    const float* col = stage + tid + q;
-    const float* h = tp - q * down;
-    const int np = q < rows ? down : rem;
-    int p = 0;
-    for (; p + 4 <= np; p += 4) {
-      a0 = fmaf(h[-p], col[p * Q], a0);
-      a1 = fmaf(h[-p - 1], col[(p + 1) * Q], a1);
-      a2 = fmaf(h[-p - 2], col[(p + 2) * Q], a2);
-      a3 = fmaf(h[-p - 3], col[(p + 3) * Q], a3);
-    }
-    for (; p < np; ++p) a0 = fmaf(h[-p], col[p * Q], a0);
-  }
-  out[j] = (a0 + a1) + (a2 + a3);
 }
 
 // Sum over the workgroup in a fixed order; the result in every thread.  sm: kT / 64 slots.
@@ -355,53 +303,26 @@ __global__ void k_al_decode(const float* __restrict__ c, i64* index, float* valu
 
 bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) == 0; }
 
-// the decimator's launch; mu: the mean to remove first (mean-first order) or null
-int al_decimate(const float* xs, i64 len, int down, const float* taps, int n_taps, float* out,
-                i64 n_out, const double* mu, hipStream_t s) {
-  // the largest of 256 / 128 / 64 outputs per workgroup whose staging fits
-  int T = kT, Q = 0;
-  for (;; T >>= 1) {
-    Q = (T + (n_taps - 1) / down) | 1;
-    if ((i64)down * Q * (i64)sizeof(float) <= kLdsBytes || T == 64) break;
-  }
-  const size_t lds = (size_t)down * Q * sizeof(float);
-  const i64 groups = (n_out + T - 1) / T;
-  if (groups > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
-  const bool vec = aligned(xs, 8);
-#define TM_AL_ENV(V, S)                                                                       \
-  hipLaunchKernelGGL((k_al_envelope<V, S>), dim3((unsigned)groups), dim3(T), lds, s, xs, len, \
-                     down, taps, n_taps, Q, out, n_out, mu)
-  if (mu) {
-    if (vec) TM_AL_ENV(true, true); else TM_AL_ENV(false, true);
-  } else {
-    if (vec) TM_AL_ENV(true, false); else TM_AL_ENV(false, false);
-  }
-#undef TM_AL_ENV
-  return TOMATIS_OK;
-}
-
-int al_env_args(const float* x, int64_t n_total, int64_t start, int64_t len, int32_t down,
-                const float* taps, int32_t n_taps, float* out, double* out_mean) {
-  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
-      len > n_total - start || down < 2 || n_taps < 1 || (n_taps & 1) == 0)
-    return TOMATIS_E_ARG;
-  if (down > kMaxDown || n_taps > 20 * down + 1) return TOMATIS_E_UNSUPPORTED;
-  return TOMATIS_OK;
-}
-
 // ---------------------------------------------------------------------------
-// rational-ratio decimator: resample_poly(e, up, down), 1 <= up < down
+// the decimator: resample_poly(e, up, down), 1 <= up < down
 // ---------------------------------------------------------------------------
 // With c = down j + half, p = c mod up and ih = c / up, output j is
 //   y[j] = sum_v taps[p + up (K - 1 - v)] e[ih - (K - 1) + v],  v < K = ceil(n_taps / up)
-// (a tap index >= n_taps counts as a zero tap).  A workgroup of kT threads owns
+// (a tap index >= n_taps counts as a zero tap; for up == 1 this is y[j] =
+// sum_u taps[n_taps - 1 - u] e[down j - half + u]).  e is formed from 8-byte
+// stereo loads as it is staged (the PCM is read once; the halo of neighbouring
+// tiles comes from L2), less float32(mu[0]) inside the range in the mean-first
+// order (SUB; compare_audio.py:33-34 removes the mean before it decimates),
+// and is zero outside the range.  A workgroup of kT threads owns
 // T consecutive outputs, S = kT / T threads each: thread (o, si) = (tid % T,
 // tid / T) sums the terms v in [si C, (si + 1) C) of output j0 + o in four
 // chains joined pairwise (up > 1: by v mod 4; up == 1: by the place in a row
-// of down samples, k_al_envelope's order); the S partial sums are added in the
-// order of si.  T, S and C depend on (up, down, n_taps) alone, and a tile's
-// result does not depend on the workgroup that computes it: the workgroups
-// are resident and walk the tiles, so each builds its tap table once.
+// of down samples, the tail of a row on the first chain); the S partial sums
+// are added in the order of si.  T, S and C depend on (up, down, n_taps)
+// alone, and a tile's result does not depend on the workgroup that computes
+// it: the workgroups are resident and walk the tiles, so each builds its tap
+// table once.  With the reference's 20 down + 1 taps, up == 1 runs 256 x 1 up
+// to down = 53 (48 kHz: 24, 96 kHz: 48), 128 x 2 up to 95, 64 x 4 from 96 (192 kHz) on.
 //   stage: the W samples from g0 = ih(j0) - (K - 1) on; sample g0 + i at word
 //          i + pad (i / down).  pad = 1 for up == 1 and an even down: lane o
 //          then starts at o (down + 1), an odd stride over the 32 banks of a
@@ -421,20 +342,20 @@ int al_env_args(const float* x, int64_t n_total, int64_t start, int64_t len, int
 //   red:   the kT partial sums.
 constexpr int kRatMaxDown = 512;
 constexpr int kRatMaxUp = 64;
-constexpr int kRatLdsBytes = 64 * 1024;
+constexpr int kEnvLdsBytes = 64 * 1024;
 
-struct RatPlan {
+struct EnvPlan {
   int up, down, n_taps, K, Ks, T, C, W, pad, stage_words, tab_words;
 };
 
-__device__ __forceinline__ float rat_join(float a0, float a1, float a2, float a3) {
+__device__ __forceinline__ float env_join(float a0, float a1, float a2, float a3) {
   return (a0 + a1) + (a2 + a3);
 }
 
 // up == 1, the terms v in [v, v1) row by row of down samples: tap v is h[v] (REV: h[-v]),
 // sample v lies at sp[v + pad (v / down)]
 template <bool REV>
-__device__ __forceinline__ float rat_rows(const float* __restrict__ h, const float* sp, int v,
+__device__ __forceinline__ float env_rows(const float* __restrict__ h, const float* sp, int v,
                                           int v1, int down, int pad) {
   float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
   while (v < v1) {
@@ -449,15 +370,15 @@ __device__ __forceinline__ float rat_rows(const float* __restrict__ h, const flo
     }
     for (; v < ve; ++v) a0 = fmaf(REV ? h[-v] : h[v], col[v], a0);
   }
-  return rat_join(a0, a1, a2, a3);
+  return env_join(a0, a1, a2, a3);
 }
 
 // TAPS: 0 up > 1, the phase table in LDS; 1 up == 1, taps from global memory;
 // 2 up == 1, the reversed taps in LDS
 template <bool VEC, bool SUB, bool MONO, int TAPS>
-__global__ __launch_bounds__(kT) void k_al_envelope_rat(const float* __restrict__ x, i64 len,
+__global__ __launch_bounds__(kT) void k_al_envelope(const float* __restrict__ x, i64 len,
                                                          const float* __restrict__ taps,
-                                                         RatPlan pl, float* __restrict__ out,
+                                                         EnvPlan pl, float* __restrict__ out,
                                                          i64 n_out, int tiles,
                                                          const double* __restrict__ mu) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -515,9 +436,9 @@ __global__ __launch_bounds__(kT) void k_al_envelope_rat(const float* __restrict_
       if constexpr (TAPS != 0) {
         const float* sp = stage + o * (down + pl.pad);  // sample o down
         if constexpr (TAPS == 1)
-          part = rat_rows<true>(taps + (pl.n_taps - 1), sp, v0, v1, down, pl.pad);
+          part = env_rows<true>(taps + (pl.n_taps - 1), sp, v0, v1, down, pl.pad);
         else
-          part = rat_rows<false>(tab, sp, v0, v1, down, pl.pad);
+          part = env_rows<false>(tab, sp, v0, v1, down, pl.pad);
       } else {
         const int xo = p0 + down * o, ao = xo / up, p = xo - ao * up;
         const float* sp = stage + ao;
@@ -533,7 +454,7 @@ __global__ __launch_bounds__(kT) void k_al_envelope_rat(const float* __restrict_
           a3 = fmaf(t.w, sp[v + 3], a3);
         }
         for (; v < v1; ++v) a0 = fmaf(h[v], sp[v], a0);
-        part = rat_join(a0, a1, a2, a3);
+        part = env_join(a0, a1, a2, a3);
       }
     }
     if (T == kT) {
@@ -552,7 +473,7 @@ __global__ __launch_bounds__(kT) void k_al_envelope_rat(const float* __restrict_
 
 // the largest T = 256, 128, ... 1 outputs per workgroup whose staging fits beside the tap
 // table (lds_taps) or alone (up == 1 only)
-bool rat_plan_for(int up, int down, int n_taps, bool lds_taps, RatPlan* pl) {
+bool env_plan_for(int up, int down, int n_taps, bool lds_taps, EnvPlan* pl) {
   pl->up = up, pl->down = down, pl->n_taps = n_taps;
   pl->K = (n_taps + up - 1) / up;
   pl->Ks = 4 * (((pl->K + 3) / 4) | 1);
@@ -565,41 +486,86 @@ bool rat_plan_for(int up, int down, int n_taps, bool lds_taps, RatPlan* pl) {
     pl->W = (up - 1 + down * (T - 1)) / up + pl->K;
     pl->stage_words = (pl->W + pl->pad * (pl->W / down + 1) + 3) / 4 * 4;
     const size_t bytes = sizeof(float) * ((size_t)pl->stage_words + pl->tab_words + kT);
-    if (bytes <= (size_t)kRatLdsBytes) return true;
+    if (bytes <= (size_t)kEnvLdsBytes) return true;
     if (T == 1) return false;
   }
 }
 
-bool rat_plan(int up, int down, int n_taps, RatPlan* pl) {
-  if (rat_plan_for(up, down, n_taps, true, pl) && (up > 1 || pl->T >= 64)) return true;
-  return up == 1 && rat_plan_for(up, down, n_taps, false, pl);
+bool env_plan(int up, int down, int n_taps, EnvPlan* pl) {
+  if (env_plan_for(up, down, n_taps, true, pl) && (up > 1 || pl->T >= 64)) return true;
+  return up == 1 && env_plan_for(up, down, n_taps, false, pl);
 }
 
-int al_decimate_rat(const float* xs, i64 len, bool mono, const float* taps, const RatPlan& pl,
-                    float* out, i64 n_out, const double* mu, hipStream_t s) {
+// the decimator's launch; mu: the mean to remove first (mean-first order) or null
+int al_decimate(const float* xs, i64 len, bool mono, const float* taps, const EnvPlan& pl,
+                float* out, i64 n_out, const double* mu, hipStream_t s) {
   const size_t lds = sizeof(float) * ((size_t)pl.stage_words + pl.tab_words + kT);
   const i64 tiles = (n_out + pl.T - 1) / pl.T;
   if (tiles > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
   const i64 cap = (i64)al_cus() * 4;  // resident workgroups, each builds its phase table once
   const unsigned groups = (unsigned)(tiles < cap ? tiles : cap);
   const bool vec = !mono && aligned(xs, 8);
-#define TM_AL_RAT(V, S, M, U)                                                               \
-  hipLaunchKernelGGL((k_al_envelope_rat<V, S, M, U>), dim3(groups), dim3(kT), lds, s, xs, len, \
+#define TM_AL_ENV(V, S, M, U)                                                               \
+  hipLaunchKernelGGL((k_al_envelope<V, S, M, U>), dim3(groups), dim3(kT), lds, s, xs, len, \
                      taps, pl, out, n_out, (int)tiles, mu)
-#define TM_AL_RAT_U(V, S, M)                             \
+#define TM_AL_ENV_U(V, S, M)                             \
   do {                                                   \
-    if (pl.up > 1) TM_AL_RAT(V, S, M, 0);                \
-    else if (pl.tab_words == 0) TM_AL_RAT(V, S, M, 1);   \
-    else TM_AL_RAT(V, S, M, 2);                          \
+    if (pl.up > 1) TM_AL_ENV(V, S, M, 0);                \
+    else if (pl.tab_words == 0) TM_AL_ENV(V, S, M, 1);   \
+    else TM_AL_ENV(V, S, M, 2);                          \
   } while (0)
-#define TM_AL_RAT_S(V, M) \
-  do { if (mu) TM_AL_RAT_U(V, true, M); else TM_AL_RAT_U(V, false, M); } while (0)
-  if (mono) TM_AL_RAT_S(false, true);
-  else if (vec) TM_AL_RAT_S(true, false);
-  else TM_AL_RAT_S(false, false);
-#undef TM_AL_RAT_S
-#undef TM_AL_RAT_U
-#undef TM_AL_RAT
+#define TM_AL_ENV_S(V, M) \
+  do { if (mu) TM_AL_ENV_U(V, true, M); else TM_AL_ENV_U(V, false, M); } while (0)
+  if (mono) TM_AL_ENV_S(false, true);
+  else if (vec) TM_AL_ENV_S(true, false);
+  else TM_AL_ENV_S(false, false);
+#undef TM_AL_ENV_S
+#undef TM_AL_ENV_U
+#undef TM_AL_ENV
+  return TOMATIS_OK;
+}
+
+// The envelope of one range with its mean removed, out_mean[0] the mean, out_mean[1..] the
+// partial sums.  Mean first: the float64 mean of e, then the decimator on e - float32(mean).
+// Mean last: the decimator, then the float64 mean of its output, then the centring pass.
+int al_envelope(const float* xs, i64 len, int channels, int up, int down, const float* taps,
+                int n_taps, bool mean_first, float* out, double* out_mean, hipStream_t s) {
+  EnvPlan pl;
+  if (!env_plan(up, down, n_taps, &pl)) return TOMATIS_E_UNSUPPORTED;
+  const bool mono = channels == 1;
+  const i64 n_out = (len * up + down - 1) / down;
+  double* part = out_mean + 1;
+  int rc;
+  if (mean_first) {
+    const int G = sum_groups(len);
+    if (mono)
+      hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, xs, len, part);
+    else if (aligned(xs, 8))
+      hipLaunchKernelGGL(k_al_pm_sum<true>, dim3(G), dim3(kT), 0, s, xs, len, part);
+    else
+      hipLaunchKernelGGL(k_al_pm_sum<false>, dim3(G), dim3(kT), 0, s, xs, len, part);
+    hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)part, G, 0, 1, len,
+                       out_mean);
+    rc = al_decimate(xs, len, mono, taps, pl, out, n_out, out_mean, s);
+    return rc != TOMATIS_OK ? rc : al_launch();
+  }
+  rc = al_decimate(xs, len, mono, taps, pl, out, n_out, nullptr, s);
+  if (rc != TOMATIS_OK) return rc;
+  const int G = sum_groups(n_out);
+  hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, part);
+  const i64 want = (n_out + kT - 1) / kT, cap = (i64)al_cus() * 8;
+  hipLaunchKernelGGL(k_al_center, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, out,
+                     n_out, (const double*)part, G, out_mean);
+  return al_launch();
+}
+
+// tomatis_align_envelope[_mean_first]: stereo, up == 1, down <= kMaxDown
+int al_env_args(const float* x, int64_t n_total, int64_t start, int64_t len, int32_t down,
+                const float* taps, int32_t n_taps, float* out, double* out_mean) {
+  if (!x || !taps || !out || !out_mean || n_total < 0 || start < 0 || len < 1 ||
+      len > n_total - start || down < 2 || n_taps < 1 || (n_taps & 1) == 0)
+    return TOMATIS_E_ARG;
+  if (down > kMaxDown || n_taps > 20 * down + 1) return TOMATIS_E_UNSUPPORTED;
   return TOMATIS_OK;
 }
 
@@ -618,88 +584,39 @@ int tomatis_align_envelope_rational(const float* x, int64_t n_total, int64_t sta
   if (down > kRatMaxDown || up > kRatMaxUp || n_taps > 20 * down + 1 ||
       len > (int64_t)1 << 55)
     return TOMATIS_E_UNSUPPORTED;
-  RatPlan pl;
-  if (!rat_plan((int)up, (int)down, (int)n_taps, &pl)) return TOMATIS_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)hs;
-  const bool mono = channels == 1;
-  const float* xs = x + (i64)channels * start;
-  const i64 n_out = ((i64)len * up + down - 1) / down;
-  int rc;
-  if (mean_first) {
-    const i64 want = ((i64)len + kT - 1) / kT;
-    const int G = (int)(want < kSumGroups ? want : kSumGroups);
-    if (mono)
-      hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
-    else if (aligned(xs, 8))
-      hipLaunchKernelGGL(k_al_pm_sum<true>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
-    else
-      hipLaunchKernelGGL(k_al_pm_sum<false>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
-    hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out_mean + 1), G, 0, 1,
-                       (i64)len, out_mean);
-    rc = al_decimate_rat(xs, (i64)len, mono, taps, pl, out, n_out, out_mean, s);
-    return rc != TOMATIS_OK ? rc : al_launch();
-  }
-  rc = al_decimate_rat(xs, (i64)len, mono, taps, pl, out, n_out, nullptr, s);
-  if (rc != TOMATIS_OK) return rc;
-  const i64 want = (n_out + kT - 1) / kT;
-  const int G = (int)(want < kSumGroups ? want : kSumGroups);
-  hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, out_mean + 1);
-  const i64 cap = (i64)al_cus() * 8;
-  hipLaunchKernelGGL(k_al_center, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, out,
-                     n_out, (const double*)(out_mean + 1), G, out_mean);
-  return al_launch();
+  return al_envelope(x + (i64)channels * start, (i64)len, (int)channels, (int)up, (int)down, taps,
+                     (int)n_taps, mean_first != 0, out, out_mean, (hipStream_t)hs);
 }
 
 int tomatis_align_envelope_mean_first(const float* x, int64_t n_total, int64_t start, int64_t len,
                                       int32_t down, const float* taps, int32_t n_taps, float* out,
                                       double* out_mean, void* hs) {
-  int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
+  const int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
   if (rc != TOMATIS_OK) return rc;
-  hipStream_t s = (hipStream_t)hs;
-  const float* xs = x + 2 * start;
-  const i64 want = ((i64)len + kT - 1) / kT;
-  const int G = (int)(want < kSumGroups ? want : kSumGroups);
-  if (aligned(xs, 8))
-    hipLaunchKernelGGL(k_al_pm_sum<true>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
-  else
-    hipLaunchKernelGGL(k_al_pm_sum<false>, dim3(G), dim3(kT), 0, s, xs, (i64)len, out_mean + 1);
-  hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out_mean + 1), G, 0, 1,
-                     (i64)len, out_mean);
-  rc = al_decimate(xs, (i64)len, (int)down, taps, (int)n_taps, out, ((i64)len + down - 1) / down,
-                   out_mean, s);
-  return rc != TOMATIS_OK ? rc : al_launch();
+  return al_envelope(x + 2 * start, (i64)len, 2, 1, (int)down, taps, (int)n_taps, true, out,
+                     out_mean, (hipStream_t)hs);
+}
+
+int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
+                           int32_t down, const float* taps, int32_t n_taps, float* out,
+                           double* out_mean, void* hs) {
+  const int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
+  if (rc != TOMATIS_OK) return rc;
+  return al_envelope(x + 2 * start, (i64)len, 2, 1, (int)down, taps, (int)n_taps, false, out,
+                     out_mean, (hipStream_t)hs);
 }
 
 int tomatis_compare_residual(const float* b, const float* c, int64_t n, float gain, double* out,
                              void* hs) {
   if (!b || !c || !out || n < 1) return TOMATIS_E_ARG;
   hipStream_t s = (hipStream_t)hs;
-  const i64 want = ((i64)n + kT - 1) / kT;
-  const int G = (int)(want < kSumGroups ? want : kSumGroups);
+  const int G = sum_groups((i64)n);
   if (aligned(b, 8) && aligned(c, 8))
     hipLaunchKernelGGL(k_al_residual<true>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 2);
   else
     hipLaunchKernelGGL(k_al_residual<false>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 2);
   hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out + 2), G, kSumGroups,
                      2, (i64)n, out);
-  return al_launch();
-}
-
-int tomatis_align_envelope(const float* x, int64_t n_total, int64_t start, int64_t len,
-                           int32_t down, const float* taps, int32_t n_taps, float* out,
-                           double* out_mean, void* hs) {
-  int rc = al_env_args(x, n_total, start, len, down, taps, n_taps, out, out_mean);
-  if (rc != TOMATIS_OK) return rc;
-  hipStream_t s = (hipStream_t)hs;
-  const i64 n_out = (len + down - 1) / down;
-  rc = al_decimate(x + 2 * start, (i64)len, (int)down, taps, (int)n_taps, out, n_out, nullptr, s);
-  if (rc != TOMATIS_OK) return rc;
-  const i64 want = (n_out + kT - 1) / kT;
-  const int G = (int)(want < kSumGroups ? want : kSumGroups);
-  hipLaunchKernelGGL(k_al_sum, dim3(G), dim3(kT), 0, s, (const float*)out, n_out, out_mean + 1);
-  const i64 cap = (i64)al_cus() * 8;
-  hipLaunchKernelGGL(k_al_center, dim3((unsigned)(want < cap ? want : cap)), dim3(kT), 0, s, out,
-                     n_out, (const double*)(out_mean + 1), G, out_mean);
   return al_launch();
 }
 
