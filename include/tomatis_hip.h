@@ -316,7 +316,12 @@ int tomatis_stft_ola_pipelined(tomatis_plan_t plan, const float* x, const float*
  * frame loop; prev_plan's runs beyond this plan's run count are limited by a
  * short launch after the transform.  prev_plan must stay alive until the call's
  * work has completed.  Results are bit-identical to limiting each batch with
- * its own plan (src/process_tomatis.py:331-357, per file). */
+ * its own plan (src/process_tomatis.py:331-357, per file).
+ * These calls never return TOMATIS_OK with prev_y left unlimited.  A plan none
+ * of whose streams has a frame launches nothing, so these calls (and the two
+ * above, which go through them) return TOMATIS_E_UNSUPPORTED for it before any
+ * launch, prev_y untouched: the caller limits prev_y with
+ * tomatis_apply_limiter(prev_plan, ...) and runs this batch unpipelined. */
 int tomatis_stft_ola_gated_pipelined_after(tomatis_plan_t plan, const float* x,
                                            const float* gain_rows, int32_t n_rows, float* y,
                                            uint32_t* chunk_peak_bits, float limit, float* r_out,

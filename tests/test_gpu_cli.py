@@ -229,3 +229,110 @@ def test_batch_runner_pipelined_batches(tmp_path, mode, extra):
         ref = orc.process_standard(x, sr, gate_ui=50, n_fft=2048, hop=512)
         N = lens[3]
         _cmp(y, ref["y"], ref["wsum"][ref["pad"]:ref["pad"] + N] >= 1e-3)
+
+
+# batch.py's unlike hand-offs.  Per-file lengths (samples at 48 kHz, stereo; no
+# file longer than 5 s) and the batch budget in samples: split_batches is
+# greedy, so a batch is closed only by a file that does not fit -- the batch
+# before a tiny file sums exactly to the budget, or the tiny file would join it.
+_SR = 48000
+_A4 = [144017, 96003, 124800, 153605]            # 518425 <= budget
+_B2 = [240001, 230409]                           # 470410, + 96001 > budget
+_C5 = [96001, 105603, 120000, 100805, 115207]    # 537616 == budget
+UNLIKE_ORDERS = {
+    # adaptive: AdaptiveGroups -> AdaptivePipeline -> AdaptiveGroups -> a last
+    # file of 700 samples (no frame)
+    "4_2_5_1": dict(lens=_A4 + _B2 + _C5 + [700], budget=537616, sizes=[4, 2, 5, 1],
+                    loud=[0, 3, 10], check=[0, 3, 10]),
+    # AdaptivePipeline -> AdaptiveGroups -> a single 5 s file -> AdaptiveGroups
+    "2_4_1_4": dict(lens=[200001, 230003, 100001, 120003, 130005, 110007, 240000,
+                          235001, 80003, 70005, 84000], budget=470000, sizes=[2, 4, 1, 4],
+                    loud=[1, 2, 5, 6, 7, 10], check=[2, 5, 6]),
+    # standard / xfade: a 300-sample file (no frame) as a middle batch and as the
+    # last one, each after a loud file
+    "2_1_1_1": dict(lens=[130001, 109999, 300, 239900, 300], budget=240000, sizes=[2, 1, 1, 1],
+                    loud=[1, 3], check=[1, 3]),
+}
+
+
+def _unlike_files(tmp_path, spec):
+    """The order's files (loud ones: gain 1.4, else 0.2) and the batch.py
+    arguments that give its batch sizes (asserted with split_batches)."""
+    from tomatis_audio_processor_amd import batch
+    xs, files = [], []
+    for i, n in enumerate(spec["lens"]):
+        x = (synth_stream(400 + i, n, 2, _SR) * np.float32(1.4 if i in spec["loud"] else 0.2))
+        xs.append(x.astype(np.float32))   # (FLOAT WAV: exact)
+        files.append(_wav(tmp_path, f"h{i}.wav", xs[-1], _SR))
+    gb = repr(spec["budget"] * 2 * 4 / 2 ** 30)   # (exact: a power-of-two divisor)
+    ids = list(range(len(files)))
+    split = batch.split_batches(ids, {i: spec["lens"][i] * 2 for i in ids},
+                                max(1, int(float(gb) * 2 ** 30 / 4)))
+    assert [len(b) for b in split] == spec["sizes"]
+    return xs, files, ["-i", *files, "--batch_gb", gb, "--n_fft", "2048", "--hop", "512"]
+
+
+def _same_as_unpipelined(tmp_path, args, n_files, ext="wav"):
+    """Run batch.py pipelined and with --no_pipeline: every output file and the
+    manifest byte-identical.  Returns the pipelined run's output directory."""
+    from tomatis_audio_processor_amd import batch
+    od1, od2 = str(tmp_path / "p"), str(tmp_path / "u")
+    assert batch.main(args + ["--out_dir", od1]) == 0
+    assert batch.main(args + ["--out_dir", od2, "--no_pipeline"]) == 0
+    for i in range(n_files):
+        a = open(os.path.join(od1, f"h{i}_tomatis.{ext}"), "rb").read()
+        b = open(os.path.join(od2, f"h{i}_tomatis.{ext}"), "rb").read()
+        assert a == b, f"file {i} differs from --no_pipeline"
+    assert (open(os.path.join(od1, "manifest.json"), "rb").read()
+            == open(os.path.join(od2, "manifest.json"), "rb").read())
+    return od1
+
+
+@pytest.mark.parametrize("order", ["4_2_5_1", "2_4_1_4"])
+def test_batch_runner_pipelined_unlike_adaptive(tmp_path, order):
+    """batch.py --mode adaptive over batches of 4 or more files (AdaptiveGroups)
+    and of 1 to 3 (AdaptivePipeline), the last one a file without a frame:
+    byte-identical to --no_pipeline, and against the oracle a limited file of
+    each group of the first 4-file batch and of the batch handed to the
+    no-frame batch (2_4_1_4: the single file, limited inside the next batch's
+    launch)."""
+    _gpu()
+    spec = UNLIKE_ORDERS[order]
+    xs, files, args = _unlike_files(tmp_path, spec)
+    od = _same_as_unpipelined(tmp_path, args + ["--mode", "adaptive"], len(files))
+    for i in spec["check"]:
+        ref = orc.process_adaptive(xs[i], _SR, n_fft=2048, hop=512)
+        assert ref["scale"] is not None and ref["scale"] < 1.0, f"file {i} is meant to be limited"
+        y, _ = audio_io.read(os.path.join(od, f"h{i}_tomatis.wav"))
+        _cmp(y, ref["y"], ref["wsum"] >= 1e-3)
+    if order == "4_2_5_1":      # the file without a frame: 700 zeros
+        y, _ = audio_io.read(os.path.join(od, f"h{len(files) - 1}_tomatis.wav"))
+        assert y.shape == (700, 2) and not y.any()
+
+
+def test_batch_runner_pipelined_unlike_adaptive_flac(tmp_path):
+    """The same job written as FLAC from the device (--out_ext flac)."""
+    _gpu()
+    spec = UNLIKE_ORDERS["4_2_5_1"]
+    xs, files, args = _unlike_files(tmp_path, spec)
+    _same_as_unpipelined(tmp_path, args + ["--mode", "adaptive", "--out_ext", "flac"],
+                         len(files), ext="flac")
+
+
+@pytest.mark.parametrize("mode", ["standard", "xfade"])
+def test_batch_runner_pipelined_no_frame_batches(tmp_path, mode):
+    """A 300-sample file (no frame at 2048 / 512: it launches nothing) as a
+    middle batch and as the last one: the batch before it is limited on its own
+    plan.  Byte-identical to --no_pipeline; the loud file before each against
+    the oracle."""
+    _gpu()
+    spec = UNLIKE_ORDERS["2_1_1_1"]
+    xs, files, args = _unlike_files(tmp_path, spec)
+    od = _same_as_unpipelined(tmp_path, args + ["--mode", mode], len(files))
+    kw = dict(xfade_ms=500.0) if mode == "xfade" else {}
+    for i in spec["check"]:
+        N = len(xs[i])
+        ref = orc.process_standard(xs[i], _SR, gate_ui=50, n_fft=2048, hop=512, **kw)
+        assert any(s is not None and s < 1.0 for s in ref["scales"]), f"file {i} is meant to be limited"
+        y, _ = audio_io.read(os.path.join(od, f"h{i}_tomatis.wav"))
+        _cmp(y, ref["y"], ref["wsum"][ref["pad"]:ref["pad"] + N] >= 1e-3)

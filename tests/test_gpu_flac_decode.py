@@ -170,3 +170,28 @@ def test_device_decode_corrupted_bytes(tmp_path):
         want = (ref.astype(np.float64) / float(1 << (bps - 1))).astype(np.float32)
         assert (n, ch) == ref.shape, (t, pos)
         assert np.array_equal(got[:n * ch].cpu().numpy().reshape(n, ch), want), (t, pos)
+
+
+def test_streaminfo_total_does_not_size_the_staging(tmp_path, monkeypatch):
+    """A STREAMINFO total of 2^32 samples over 12 K samples of frames (a
+    damaged header; the frames do not chain to it, so the host decoder
+    decides): the read returns what the host decoder returns, and no
+    page-locked block is sized by the header's claim (32 GiB of int32 stereo)
+    -- the bytes of the file bound it."""
+    torch, audio_io, fileio = _mods()
+    from tests.test_gpu_flac_device import _signals
+    x = _signals(np.random.default_rng(5), 4096 * 3 + 301, 24)["tone_noise"]
+    b = bytearray(audio_io.flac_encode_int(np.ascontiguousarray(x), 44100, 24))
+    assert bytes(b[:4]) == b"fLaC" and (b[4] & 0x7F) == 0   # STREAMINFO first
+    b[21] = (b[21] & 0xF0) | 1  # total samples: the low nibble and four bytes
+    b[22:26] = bytes(4)
+    assert audio_io.flac_info_bytes(bytes(b))[3] == 1 << 32
+    empty = torch.empty
+
+    def guarded(*size, **kw):
+        if kw.get("pin_memory"):
+            n = int(np.prod(size[0] if len(size) == 1 and not isinstance(size[0], int) else size))
+            assert n * 4 <= 1 << 32, f"a page-locked block of {n} elements for a {len(b)}-byte file"
+        return empty(*size, **kw)
+    monkeypatch.setattr(torch, "empty", guarded)
+    _check(torch, audio_io, fileio, tmp_path, bytes(b), "claims_2p32", expect_device=False)

@@ -3066,6 +3066,9 @@ int tomatis_stft_ola_gated_pipelined_after(tomatis_plan_t p, const float* x, con
   if (!gated_eligible(p) || p->total_chunks <= 0 || !p->chunk_need || p->SH > 8)
     return TOMATIS_E_UNSUPPORTED;
   if (!gated_rows_ok(p, n_rows)) return TOMATIS_E_ARG;
+  // a plan without a frame launches nothing, so it has no frame loop to limit
+  // prev_y in: declined before any launch (never TOMATIS_OK with prev_y unlimited)
+  if (p->n_runs == 0) return TOMATIS_E_UNSUPPORTED;
   const tomatis_plan_s* q = prev_plan ? prev_plan : p;
   if (prev_y && !prev_plan_ok(p, q)) return TOMATIS_E_UNSUPPORTED;
   const GateOut g{r_out, states_out, true};
@@ -3107,6 +3110,8 @@ int tomatis_stft_ola_pipelined_after(tomatis_plan_t p, const float* x, const flo
   if (p->generic || p->lds || p->NR != 32 || p->SH > 8 || !(p64 || p128) ||
       p->total_chunks <= 0 || !p->chunk_need)
     return TOMATIS_E_UNSUPPORTED;
+  // (a plan without a frame: as tomatis_stft_ola_gated_pipelined_after)
+  if (p->n_runs == 0) return TOMATIS_E_UNSUPPORTED;
   const tomatis_plan_s* q = prev_plan ? prev_plan : p;
   if (prev_y && !prev_plan_ok(p, q)) return TOMATIS_E_UNSUPPORTED;
   const PrevBatch pb{prev_y, prev_peaks, q};

@@ -852,6 +852,24 @@ class AdaptivePipeline:
                                              ptr(self.peaks), PEAK_LIMIT, stream_handle()),
               "stft_ola_limited")
 
+    def _take_prev(self, prev_pipe, strm, cur):
+        """The pending pass this transform limits: ``prev_pipe`` itself, or the
+        first pending group of an AdaptiveGroups (a launch has one partner: the
+        other pending groups are limited now, on their own plans and streams).
+        ``strm``, this pipeline's stream, waits for every such member's stream
+        (``cur`` for a member without one), so all of ``prev_pipe`` is final
+        once this pass's work on ``strm`` has completed."""
+        if prev_pipe is None:
+            return None
+        members = [q for q in getattr(prev_pipe, "pipes", [prev_pipe]) if q.pending]
+        for q in members[1:]:
+            q.flush()
+        for q in members:
+            qs = getattr(q, "stream", None) or cur
+            if qs != strm:
+                strm.wait_stream(qs)
+        return members[0] if members else None
+
     def _pipelined_pass(self) -> bool:
         a = self._after
         # the other buffer while this pipeline's own previous pass is pending,
@@ -910,10 +928,11 @@ class AdaptivePipeline:
         the device (the input peaks, the frame r) and before the transform, so a
         driver can interleave several pipelines on their own streams
         (AdaptiveGroups).  ``after``: a callable giving an event (or a list of
-        events) the transform waits for.  ``prev_pipe``: as GatePipeline.run
-        (the caller orders that pipeline's stream before this one's)."""
+        events) the transform waits for.  ``prev_pipe``: as GatePipeline.run;
+        an AdaptivePipeline or an AdaptiveGroups (``_take_prev``)."""
         torch = _torch()
-        strm = self.stream or torch.cuda.current_stream()
+        cur = torch.cuda.current_stream()
+        strm = self.stream or cur
         L, P = lib(), self.plan.h
         ss = self.ss
         sts = self.plan.streams
@@ -1033,9 +1052,9 @@ class AdaptivePipeline:
                 for e in (evs if isinstance(evs, (list, tuple)) else [evs]):
                     if e is not None:
                         strm.wait_event(e)
+            self._after = self._take_prev(prev_pipe, strm, cur)
             if marks and marks[0] is not None:
                 marks[0].record()
-            self._after = prev_pipe if (prev_pipe is not None and prev_pipe.pending) else None
             self._transform()
             if marks and marks[1] is not None:
                 marks[1].record()

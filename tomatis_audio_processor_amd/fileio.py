@@ -238,6 +238,12 @@ def _decode_flac_ranges(h, torch, buf, size, path, timer):
         got_ = C.c_int64()
         _err(h.tomatis_flac_decode(buf, size, None, 0, C.byref(got_)), "FLAC decode failed")
         n = got_.value
+    # STREAMINFO's total is the file's claim (36 bits: a damaged header can say
+    # 2^36 samples, 512 GiB of page-locked int32 stereo); the buffers hold what
+    # the bytes can: a frame is at most 65535 samples and, with its header,
+    # one constant subframe and both CRCs, more than 8 bytes.  A total above
+    # that is never reached, so the whole-buffer decoder decides, as below.
+    n = min(n, (size // 8 + 1) * 65535)
     pin = torch.empty(max(1, n * ch), dtype=torch.int32, pin_memory=True)
     dev = torch.empty(max(1, n * ch), dtype=torch.int32, device="cuda")
     cs = torch.cuda.Stream()
