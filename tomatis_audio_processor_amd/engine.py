@@ -16,6 +16,7 @@ Reference behaviour reproduced per mode (file:line):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -375,11 +376,183 @@ def _check_fft(n_fft, hop, ch):
         raise ValueError(f"{ch} channels: the gfx950 kernels handle 1 to {MAX_CHANNELS} channels")
 
 
+def _result(pipe, streams, out_lens, extra, **arrays) -> Result:
+    """A pipeline's Result: the per-stream lists of its plan's ``streams``."""
+    return Result(y=pipe.y, out_offs=pipe.out_offs, out_lens=out_lens, ch=pipe.ss.ch,
+                  frame_base=[s.frame_base for s in streams],
+                  n_frames=[s.n_frames for s in streams],
+                  first_start=[s.first_start for s in streams], hop=pipe.hop,
+                  chunk_peaks=pipe.peaks, chunk_base=[s.chunk_base for s in streams],
+                  n_chunks=[s.n_chunks for s in streams],
+                  extra=dict(extra, n_fft=pipe.n_fft, out_begin=[s.out_begin for s in streams]),
+                  **arrays)
+
+
+# ---------------------------------------------------------------------------
+# the pipelined pass hand-off (standard / xfade / adaptive)
+# ---------------------------------------------------------------------------
+
+_NO_STREAM = contextlib.nullcontext()
+
+
+class _Pipelined:
+    """The batch pipeline of GatePipeline and AdaptivePipeline: a pass leaves
+    its output unscaled in one of two buffers (``_ys`` / ``_pks``; ``y`` and
+    ``peaks`` are the current one, ``pending`` while it awaits its limiter),
+    and the next pass -- of this pipeline, or of the one that gets this one as
+    ``run(prev_pipe=...)`` -- applies that limiter inside its own transform
+    launch.  What the library declines is flushed on its own plan.  The
+    subclass provides plan, ss, gains, n_rows, rows, y and peaks."""
+
+    def _init_pipelined(self, pipelined, second_buffer, out2=None):
+        """``out2``: the second output buffer when the first one is shared."""
+        self.stream = None        # torch stream the pipeline runs on (None: the current one)
+        self.pipelined = bool(pipelined)
+        self.pending = False      # pipelined: self.y awaits its limiter
+        self._after = None        # run(prev_pipe=...): another pipeline's pending pass
+        self._cur = 0
+        if out2 is None and self.pipelined and second_buffer:
+            out2 = self.y.new_empty(self.y.shape)
+        self._ys = [self._clear_idle(self.y), self._clear_idle(out2)]
+        self._pks = [self.peaks, self.peaks.new_zeros(self.peaks.shape) if self.pipelined else None]
+
+    def _clear_idle(self, buf):
+        """Hook: prepare an output buffer this pipeline gets; returns it."""
+        return buf
+
+    def _on_stream(self):
+        return _NO_STREAM if self.stream is None else _torch().cuda.stream(self.stream)
+
+    @staticmethod
+    def _take_prev(prev_pipe, strm, cur, n=1):
+        """The ``n`` pending passes that ``n`` launches on ``strm`` limit (a
+        launch has one partner; None where there is none): the first pending
+        members of ``prev_pipe`` -- itself, or the groups of an AdaptiveGroups.
+        The other pending members are limited now, on their own plans and
+        streams.  ``strm`` waits for every member's stream (``cur`` for a member
+        without one), so all of ``prev_pipe`` is final once the work on ``strm``
+        has completed."""
+        if prev_pipe is None:
+            return [None] * n
+        members = list(getattr(prev_pipe, "pipes", [prev_pipe]))
+        waiting = [q for q in members if q.pending]
+        for q in waiting[n:]:
+            q.flush()
+        for q in members:
+            qs = q.stream or cur
+            if qs != strm:
+                strm.wait_stream(qs)
+        return waiting[:n] + [None] * (n - len(waiting))
+
+    def _after_prev(self, prev, run_pass, *args):
+        """``run_pass(*args)`` with ``prev`` (of ``_take_prev``) as the pass its
+        launch limits.  One partner per launch: this pipeline's own pending
+        pass is limited first.  A ``prev`` still pending afterwards (nothing
+        pipelined was launched) is flushed; after an exception nothing more is
+        launched (``prev`` stays pending: its owner's result() flushes it)."""
+        if prev is not None and prev.pending:
+            self.flush()
+            self._after = prev
+        try:
+            run_pass(*args)
+            if prev is not None and prev.pending:
+                prev.flush()
+        finally:
+            self._after = None
+
+    def _prev(self):
+        """(plan, y, peaks) of the output this launch limits: another
+        pipeline's pending pass (run(prev_pipe=...)), this pipeline's own, or
+        none."""
+        a = self._after
+        if a is not None and a.pending:
+            return a.plan, a.y, a.peaks
+        if self.pending:
+            return self.plan, self.y, self.peaks
+        return None, None, None
+
+    def _out_slot(self) -> int:
+        """The output buffer of a pipelined pass: the other one while this
+        pipeline's own previous pass is pending, else the current one."""
+        nxt = (1 - self._cur) if self.pending else self._cur
+        if self._ys[nxt] is None:   # second_buffer=False: allocated on first need
+            self._ys[nxt] = self._clear_idle(self.y.new_empty(self.y.shape))
+        return nxt
+
+    def _took_prev(self, nxt: int):
+        """Bookkeeping after a pipelined launch into buffer ``nxt``."""
+        if self._after is not None:
+            self._after.pending = False   # limited inside that launch
+        self._cur = nxt
+        self.y, self.peaks = self._ys[nxt], self._pks[nxt]
+        self.pending = True
+
+    def _pipelined_launch(self, call, what="stft_ola_pipelined") -> bool:
+        """One pipelined pass: ``call(nxt, pplan, prev_y, prev_pk) -> rc``
+        launches the transform into buffer ``nxt`` and limits the pending output
+        ``prev_y`` of ``pplan`` inside it.  Another pipeline's pass that the
+        library declines (a plan of another n_fft / hop / channel count) is
+        flushed on its own plan, and the call repeated with nothing to limit.
+        False (nothing launched; pipelining stays off) when the library declines
+        this plan's own shape."""
+        nxt = self._out_slot()
+        pplan, prev_y, prev_pk = self._prev()
+        rc = call(nxt, pplan, prev_y, prev_pk)
+        if rc == E_UNSUPPORTED and pplan is not None and pplan is not self.plan:
+            self._after.flush()
+            self._after = None
+            rc = call(nxt, None, None, None)
+        if rc == E_UNSUPPORTED:
+            self.pipelined = False
+            return False
+        check(rc, what)
+        self._took_prev(nxt)
+        return True
+
+    def _rows_call(self, nxt, pplan, prev_y, prev_pk):
+        """The transform with gain-row ids (tomatis_gate_std, tomatis_minhold_bisect)
+        as a pipelined launch (it zeroes this pass's chunk peaks)."""
+        return lib().tomatis_stft_ola_pipelined_after(
+            self.plan.h, ptr(self.ss.x), ptr(self.gains), self.n_rows, ptr(self.rows),
+            ptr(self._ys[nxt]), ptr(self._pks[nxt]), PEAK_LIMIT,
+            pplan.h if pplan is not None else None, ptr(prev_y), ptr(prev_pk), stream_handle())
+
+    def _transform(self, pipelined=True):
+        """transform + OLA + per-chunk limiter from the gain-row ids: pipelined
+        (the pending pass's limiter inside this launch), else what is pending
+        is flushed and this pass limits its own output."""
+        if not (pipelined and self.pipelined and self._pipelined_launch(self._rows_call)):
+            self.flush()
+            self._limited()
+
+    def _limited(self):
+        """transform + OLA + per-chunk limiter (fused in-kernel when chunks are short)"""
+        self.peaks.zero_()
+        check(lib().tomatis_stft_ola_limited(self.plan.h, ptr(self.ss.x), ptr(self.gains),
+                                             self.n_rows, ptr(self.rows), ptr(self.y),
+                                             ptr(self.peaks), PEAK_LIMIT, stream_handle()),
+              "stft_ola_limited")
+
+    def _redo(self):
+        """finish_plan's limiter-wait redo: unpipelined, into the same buffer."""
+        self.pending = False
+        self._limited()
+
+    def flush(self):
+        """Pipelined: apply the limiter to the last pass's output (it has no
+        next pass to do it), on the pipeline's stream; no-op otherwise."""
+        if self.pending:
+            with self._on_stream():
+                check(lib().tomatis_apply_limiter(self.plan.h, ptr(self.y), ptr(self.peaks),
+                                                  PEAK_LIMIT, stream_handle()), "apply_limiter")
+            self.pending = False
+
+
 # ---------------------------------------------------------------------------
 # standard / xfade
 # ---------------------------------------------------------------------------
 
-class GatePipeline:
+class GatePipeline(_Pipelined):
     """Standard (process_tomatis) or xfade (process_tomatis_xfade) processing."""
 
     def __init__(self, ss: StreamSet, *, gate_ui=50, gate_mode="log_percent",
@@ -489,13 +662,7 @@ class GatePipeline:
             check(lib().tomatis_plan_set_gate_alpha(self.plan.h, ptr(self.alpha)), "set_gate_alpha")
         self.gated_used = False   # the last run() took tomatis_stft_ola_gated
         self.gate_fallbacks = 0   # gated passes re-run on the two-pass chain
-        self.pipelined = bool(pipelined)
-        self.pending = False      # pipelined: self.y awaits its limiter
-        self._after = None        # run(prev_pipe=...): another pipeline's pending pass
-        if self.pipelined:
-            self._ys = [self.y, torch.empty_like(self.y) if second_buffer else None]
-            self._pks = [self.peaks, torch.zeros_like(self.peaks) if second_buffer else None]
-            self._cur = 0
+        self._init_pipelined(pipelined, second_buffer)
 
     def run(self, marks=None, check_device: bool = True, prev_pipe=None):
         """Launch the whole chain on the current stream.
@@ -509,61 +676,25 @@ class GatePipeline:
         pass is pending: this pass limits it inside its transform (pipelined
         mode), or it is flushed here; either way its output is final once this
         pass's work on the stream has completed."""
-        if prev_pipe is not None and prev_pipe.pending and self.pending:
-            self.flush()          # one predecessor per pass: ours is limited now
-        self._after = prev_pipe if (prev_pipe is not None and prev_pipe.pending) else None
-        try:
-            if self.fused_levels:
-                self.gated_used = self._gated(marks)
-                if self.gated_used:
-                    if marks:
-                        marks[1].record()
-                    self._flush_after()
-                    if check_device:
-                        self.finish()
-                    # pipelined: the output is final after the next pass or flush()
-                    return None if self.pending else self.result()
-                self.fused_levels = False  # declined: this plan's shape runs two passes
-            self._two_pass(marks)
-            self._flush_after()
-        finally:
-            self._after = None
+        prev = None
+        if prev_pipe is not None:
+            cur = _torch().cuda.current_stream()
+            prev, = self._take_prev(prev_pipe, cur, cur)
+        self._after_prev(prev, self._pass, marks)
         if check_device:
             self.finish()
+        # pipelined: the output is final after the next pass or flush()
         return None if self.pending else self.result()
 
-    def _prev(self):
-        """(plan, y, peaks) of the output this pass limits: another
-        pipeline's pending pass (run(prev_pipe=...)), this pipeline's own, or
-        none."""
-        a = self._after
-        if a is not None and a.pending:
-            return a.plan, a.y, a.peaks
-        if self.pending:
-            return self.plan, self._ys[self._cur], self._pks[self._cur]
-        return None, None, None
-
-    def _out_slot(self) -> int:
-        """The output buffer of a pipelined pass: the other one while this
-        pipeline's own previous pass is pending, else the current one."""
-        nxt = (1 - self._cur) if self.pending else self._cur
-        if self._ys[nxt] is None:   # second_buffer=False: allocated on first need
-            self._ys[nxt] = _torch().empty_like(self._ys[self._cur])
-            self._pks[nxt] = _torch().zeros_like(self._pks[self._cur])
-        return nxt
-
-    def _took_prev(self, nxt: int):
-        """Bookkeeping after a pipelined launch into buffer ``nxt``."""
-        if self._after is not None:
-            self._after.pending = False   # limited inside that launch
-        self._cur = nxt
-        self.y, self.peaks = self._ys[nxt], self._pks[nxt]
-        self.pending = True
-
-    def _flush_after(self):
-        a = self._after
-        if a is not None and a.pending:
-            a.flush()
+    def _pass(self, marks=None):
+        if self.fused_levels:
+            self.gated_used = self._gated(marks)
+            if self.gated_used:
+                if marks:
+                    marks[1].record()
+                return
+            self.fused_levels = False  # declined: this plan's shape runs two passes
+        self._two_pass(marks)
 
     def _gated(self, marks=None) -> bool:
         """levels + gate + transform + limiter in one pass over the input (the
@@ -575,7 +706,16 @@ class GatePipeline:
         if rc == E_UNSUPPORTED:
             return False
         check(rc, "gate_lookback")
-        if self.pipelined and self._pipelined_pass(marks):
+
+        def gated_call(nxt, pplan, prev_y, prev_pk):
+            if marks:  # (the call zeroes this pass's chunk peaks itself)
+                marks[0].record()
+            return L.tomatis_stft_ola_gated_pipelined_after(
+                self.plan.h, ptr(self.ss.x), ptr(self.gains), self.n_rows, ptr(self._ys[nxt]),
+                ptr(self._pks[nxt]), PEAK_LIMIT, ptr(self.r), ptr(self.states),
+                pplan.h if pplan is not None else None, ptr(prev_y), ptr(prev_pk), hs)
+
+        if self.pipelined and self._pipelined_launch(gated_call, "stft_ola_gated_pipelined"):
             return True
         self.flush()
         self.peaks.zero_()
@@ -586,37 +726,6 @@ class GatePipeline:
             ptr(self.peaks), PEAK_LIMIT, ptr(self.r), ptr(self.states), hs), "stft_ola_gated")
         return True
 
-    def _pipelined_pass(self, marks=None) -> bool:
-        """One pipelined pass, limiting the pending output (this pipeline's
-        previous pass, or run(prev_pipe=...)'s) inside the launch; False (nothing
-        launched) when the library declines the shape (then pipelining stays
-        off)."""
-        L, hs = lib(), stream_handle()
-        nxt = self._out_slot()
-        pplan, prev_y, prev_pk = self._prev()
-        if marks:  # (the call zeroes this pass's chunk peaks itself)
-            marks[0].record()
-        rc = L.tomatis_stft_ola_gated_pipelined_after(
-            self.plan.h, ptr(self.ss.x), ptr(self.gains), self.n_rows, ptr(self._ys[nxt]),
-            ptr(self._pks[nxt]), PEAK_LIMIT, ptr(self.r), ptr(self.states),
-            pplan.h if pplan is not None else None, ptr(prev_y), ptr(prev_pk), hs)
-        if rc == E_UNSUPPORTED and self._drop_foreign_prev(pplan):
-            return self._pipelined_pass(marks)  # (marks[0] recorded again: same point)
-        if rc == E_UNSUPPORTED:
-            self.pipelined = False
-            return False
-        check(rc, "stft_ola_gated_pipelined")
-        self._took_prev(nxt)
-        return True
-
-    def flush(self):
-        """Pipelined: apply the limiter to the last pass's output (it has no
-        next pass to do it); no-op otherwise."""
-        if self.pending:
-            check(lib().tomatis_apply_limiter(self.plan.h, ptr(self.y), ptr(self.peaks),
-                                              PEAK_LIMIT, stream_handle()), "apply_limiter")
-            self.pending = False
-
     def _two_pass(self, marks=None, pipelined=True):
         L, P, hs = lib(), self.plan.h, stream_handle()
         check(L.tomatis_levels(P, ptr(self.ss.x), ptr(self.r), F32, hs), "levels")
@@ -624,49 +733,9 @@ class GatePipeline:
                                  ptr(self.alpha), hs), "gate_std")
         if marks:
             marks[0].record()
-        if not (pipelined and self.pipelined and self._rows_pipelined_pass()):
-            self.flush()
-            self._limited()
+        self._transform(pipelined)
         if marks:
             marks[1].record()
-
-    def _rows_pipelined_pass(self) -> bool:
-        """The two-pass chain's transform as a pipelined pass (gain-row ids from
-        tomatis_gate_std); False (nothing launched) when the library declines."""
-        nxt = self._out_slot()
-        pplan, prev_y, prev_pk = self._prev()
-        rc = lib().tomatis_stft_ola_pipelined_after(  # (zeroes this pass's chunk peaks)
-            self.plan.h, ptr(self.ss.x), ptr(self.gains), self.n_rows, ptr(self.rows),
-            ptr(self._ys[nxt]), ptr(self._pks[nxt]), PEAK_LIMIT,
-            pplan.h if pplan is not None else None, ptr(prev_y), ptr(prev_pk), stream_handle())
-        if rc == E_UNSUPPORTED and self._drop_foreign_prev(pplan):
-            return self._rows_pipelined_pass()
-        if rc == E_UNSUPPORTED:
-            self.pipelined = False
-            return False
-        check(rc, "stft_ola_pipelined")
-        self._took_prev(nxt)
-        return True
-
-    def _drop_foreign_prev(self, pplan) -> bool:
-        """A pipelined call declined another pipeline's pending pass (a plan of
-        another n_fft / hop / channel count): flush that one on its own plan and
-        let the caller retry with nothing to limit.  False when the decline is
-        this plan's own shape."""
-        a = self._after
-        if a is None or pplan is None or pplan is self.plan:
-            return False
-        a.flush()
-        self._after = None
-        return True
-
-    def _limited(self):
-        """transform + OLA + per-chunk limiter (fused in-kernel when chunks are short)"""
-        self.peaks.zero_()
-        check(lib().tomatis_stft_ola_limited(self.plan.h, ptr(self.ss.x), ptr(self.gains),
-                                             self.n_rows, ptr(self.rows), ptr(self.y),
-                                             ptr(self.peaks), PEAK_LIMIT, stream_handle()),
-              "stft_ola_limited")
 
     def finish(self) -> int:
         """Device checks of the last run() (finish_plan); an unresolved in-kernel
@@ -682,26 +751,16 @@ class GatePipeline:
             # a limiter-wait redo of the gated pass: the transform alone cannot
             # recompute states, so the two-pass chain runs with the unfused limiter
             return finish_plan(self.plan, redo_gate, "GatePipeline", redo_gate=redo_gate)
-
-        def redo():  # (unpipelined, into the same buffer)
-            self.pending = False
-            self._limited()
-        return finish_plan(self.plan, redo, "GatePipeline")
+        return finish_plan(self.plan, self._redo, "GatePipeline")
 
     def result(self) -> Result:
         self.flush()
         st = self.streams
-        return Result(y=self.y, out_offs=self.out_offs, out_lens=[s.out_len for s in st],
-                      ch=self.ss.ch, frame_base=[s.frame_base for s in st],
-                      n_frames=[s.n_frames for s in st],
-                      first_start=[s.first_start for s in st], hop=self.hop,
-                      states=self.states, r=self.r, alpha=self.alpha,
-                      chunk_peaks=self.peaks, chunk_base=[s.chunk_base for s in st],
-                      n_chunks=[s.n_chunks for s in st],
-                      extra=dict(Ton=self.Ton, Toff=self.Toff, T=self.T, xfade_frames=self.xf,
-                                 up_delay_samples=self.up_delay_samples, bounds=self.bounds,
-                                 n_fft=self.n_fft, norm="eps", limit=PEAK_LIMIT,
-                                 limiter_applied=True, out_begin=[s.out_begin for s in st]))
+        return _result(self, st, [s.out_len for s in st],
+                       dict(Ton=self.Ton, Toff=self.Toff, T=self.T, xfade_frames=self.xf,
+                            up_delay_samples=self.up_delay_samples, bounds=self.bounds,
+                            norm="eps", limit=PEAK_LIMIT, limiter_applied=True),
+                       states=self.states, r=self.r, alpha=self.alpha)
 
 
 def _alpha_lattice(xf: int):
@@ -722,7 +781,7 @@ def _alpha_lattice(xf: int):
 # adaptive
 # ---------------------------------------------------------------------------
 
-class AdaptivePipeline:
+class AdaptivePipeline(_Pipelined):
     """process_tomatis_adaptive: attenuation, levels, bisection, min-hold gate,
     alpha cross-fade, mixed gains, OLA, restore, global limiter."""
 
@@ -792,7 +851,6 @@ class AdaptivePipeline:
         self._lv_pin = None   # page-locked staging of r and the host levels (allocated once)
         self._lv_tmp = None   # host temporaries of the level chain (allocated once)
         self._pk_pin = torch.empty(max(1, ss.n_streams), dtype=torch.int32, pin_memory=True)
-        self.stream = None    # torch stream the pipeline runs on (None: the current one)
         self.done = torch.cuda.Event()
         self.prep_done = torch.cuda.Event()  # after the bisection / states launch
         self._tlh = torch.empty(3 * max(1, ss.n_streams), dtype=torch.float64, device=dev)
@@ -803,21 +861,13 @@ class AdaptivePipeline:
         # every output buffer this pipeline gets
         self._idle = [(o, N * ss.ch) for o, N, st in zip(out_offs, self.res_lens, streams)
                       if st.n_frames == 0 and N > 0]
-        self._clear_idle(self.y)
-        self.pipelined = bool(pipelined)
-        self.pending = False      # pipelined: self.y awaits its limiter
-        self._after = None        # run(prev_pipe=...): another pipeline's pending pass
-        if self.pipelined:
-            self._ys = [self.y, out2 if out2 is not None else
-                        (torch.empty_like(self.y) if second_buffer else None)]
-            self._clear_idle(self._ys[1])
-            self._pks = [self.peaks, torch.zeros_like(self.peaks)]
-            self._cur = 0
+        self._init_pipelined(pipelined, second_buffer, out2)
 
     def _clear_idle(self, buf):
         if buf is not None:
             for o, n in self._idle:
                 buf[o:o + n].zero_()
+        return buf
 
     def run(self, marks=None, timer=None, check_device: bool = True, prev_pipe=None):
         """``timer`` (a dict) collects synchronised wall-clock phases (profiling).
@@ -828,100 +878,11 @@ class AdaptivePipeline:
             self.finish()
         return None if self.pending else self.result()
 
-    def _transform(self):
-        """STFT-gain-OLA, normalise max(w,1e-8), restore, global limiter (one
-        chunk per stream: fused into the transform when its runs allow;
-        pipelined: the previous pass's limiter inside this transform)"""
-        a = self._after
-        if a is not None and a.pending and self.pending:
-            self.flush()          # one predecessor per pass
-        try:
-            if self.pipelined and self._pipelined_pass():
-                return
-            self.flush()
-            self._limited()
-        finally:
-            if a is not None and a.pending:
-                a.flush()
-            self._after = None
-
-    def _limited(self):
-        self.peaks.zero_()
-        check(lib().tomatis_stft_ola_limited(self.plan.h, ptr(self.ss.x), ptr(self.gains),
-                                             self.n_rows, ptr(self.rows), ptr(self.y),
-                                             ptr(self.peaks), PEAK_LIMIT, stream_handle()),
-              "stft_ola_limited")
-
-    def _take_prev(self, prev_pipe, strm, cur):
-        """The pending pass this transform limits: ``prev_pipe`` itself, or the
-        first pending group of an AdaptiveGroups (a launch has one partner: the
-        other pending groups are limited now, on their own plans and streams).
-        ``strm``, this pipeline's stream, waits for every such member's stream
-        (``cur`` for a member without one), so all of ``prev_pipe`` is final
-        once this pass's work on ``strm`` has completed."""
-        if prev_pipe is None:
-            return None
-        members = [q for q in getattr(prev_pipe, "pipes", [prev_pipe]) if q.pending]
-        for q in members[1:]:
-            q.flush()
-        for q in members:
-            qs = getattr(q, "stream", None) or cur
-            if qs != strm:
-                strm.wait_stream(qs)
-        return members[0] if members else None
-
-    def _pipelined_pass(self) -> bool:
-        a = self._after
-        # the other buffer while this pipeline's own previous pass is pending,
-        # else the current one (AdaptiveGroups: every group alternates in step)
-        nxt = (1 - self._cur) if self.pending else self._cur
-        if self._ys[nxt] is None:  # second_buffer=False, standalone: allocated on first need
-            self._ys[nxt] = _torch().empty_like(self._ys[self._cur])
-            self._clear_idle(self._ys[nxt])
-        if a is not None and a.pending:
-            pplan, prev_y, prev_pk = a.plan, a.y, a.peaks
-        elif self.pending:
-            pplan, prev_y, prev_pk = self.plan, self._ys[self._cur], self._pks[self._cur]
-        else:
-            pplan, prev_y, prev_pk = None, None, None
-        rc = lib().tomatis_stft_ola_pipelined_after(  # (zeroes this pass's chunk peaks)
-            self.plan.h, ptr(self.ss.x), ptr(self.gains), self.n_rows, ptr(self.rows),
-            ptr(self._ys[nxt]), ptr(self._pks[nxt]), PEAK_LIMIT,
-            pplan.h if pplan is not None else None, ptr(prev_y), ptr(prev_pk), stream_handle())
-        if rc == E_UNSUPPORTED and a is not None and pplan is a.plan:
-            a.flush()             # another shape: limited on its own plan, then retry
-            self._after = None
-            return self._pipelined_pass()
-        if rc == E_UNSUPPORTED:
-            self.pipelined = False
-            return False
-        check(rc, "stft_ola_pipelined")
-        if a is not None:
-            a.pending = False     # limited inside this launch
-        self._cur = nxt
-        self.y, self.peaks = self._ys[nxt], self._pks[nxt]
-        self.pending = True
-        return True
-
-    def flush(self):
-        """Pipelined: the last pass's global limiter (on the pipeline's stream)."""
-        if self.pending:
-            torch = _torch()
-            with torch.cuda.stream(self.stream or torch.cuda.current_stream()):
-                check(lib().tomatis_apply_limiter(self.plan.h, ptr(self.y), ptr(self.peaks),
-                                                  PEAK_LIMIT, stream_handle()), "apply_limiter")
-            self.pending = False
-
     def finish(self) -> int:
         """Device error check after the pass (on the pipeline's stream); a
         limiter-wait redo runs the transform unpipelined into the same buffer."""
-        torch = _torch()
-
-        def redo():
-            self.pending = False
-            self._limited()
-        with torch.cuda.stream(self.stream or torch.cuda.current_stream()):
-            return finish_plan(self.plan, redo, "AdaptivePipeline")
+        with self._on_stream():
+            return finish_plan(self.plan, self._redo, "AdaptivePipeline")
 
     def steps(self, marks=None, timer=None, after=None, prev_pipe=None):
         """The pass as a generator that yields wherever the host would wait for
@@ -1052,10 +1013,10 @@ class AdaptivePipeline:
                 for e in (evs if isinstance(evs, (list, tuple)) else [evs]):
                     if e is not None:
                         strm.wait_event(e)
-            self._after = self._take_prev(prev_pipe, strm, cur)
+            prev, = self._take_prev(prev_pipe, strm, cur)
             if marks and marks[0] is not None:
                 marks[0].record()
-            self._transform()
+            self._after_prev(prev, self._transform)
             if marks and marks[1] is not None:
                 marks[1].record()
             self.done.record()
@@ -1065,19 +1026,13 @@ class AdaptivePipeline:
     def result(self) -> Result:
         self.flush()
         st = list(self.plan.streams)[:self.ss.n_streams]
-        return Result(y=self.y, out_offs=self.out_offs, out_lens=list(self.res_lens),
-                      ch=self.ss.ch, frame_base=[s.frame_base for s in st],
-                      n_frames=[s.n_frames for s in st],
-                      first_start=[s.first_start for s in st], hop=self.hop,
-                      states=self.states, r=self.r32, alpha=self.alpha,
-                      chunk_peaks=self.peaks, chunk_base=[s.chunk_base for s in st],
-                      n_chunks=[s.n_chunks for s in st],
-                      extra=dict(levels=self.levels, thresholds=self.t_out,
-                                 atten_db=getattr(self, "atten", None),
-                                 min_hold_frames=self.mh, xfade_frames=self.xf,
-                                 prec=getattr(self, "prec", None), n_fft=self.n_fft,
-                                 norm="max", limit=PEAK_LIMIT, limiter_applied=True,
-                                 out_begin=[s.out_begin for s in st]))
+        return _result(self, st, list(self.res_lens),
+                       dict(levels=self.levels, thresholds=self.t_out,
+                            atten_db=getattr(self, "atten", None),
+                            min_hold_frames=self.mh, xfade_frames=self.xf,
+                            prec=getattr(self, "prec", None),
+                            norm="max", limit=PEAK_LIMIT, limiter_applied=True),
+                       states=self.states, r=self.r32, alpha=self.alpha)
 
 
 def merge_results(results: Sequence[Result]) -> Result:
@@ -1164,13 +1119,9 @@ class AdaptiveGroups:
         (groups it does not have are flushed)."""
         torch = _torch()
         cur = torch.cuda.current_stream()
-        prevs = []
-        if prev_pipe is not None:
-            prevs = list(getattr(prev_pipe, "pipes", [prev_pipe]))
-            for q in prevs[len(self.pipes):]:
-                q.flush()
-            for q in prevs:   # (their last transforms are ordered before cur)
-                cur.wait_stream(q.stream or cur)
+        # (the predecessor's last transforms are ordered before cur; its groups
+        # are pending all together or not at all, _lockstep: partner g is group g)
+        prevs = _Pipelined._take_prev(prev_pipe, cur, cur, len(self.pipes))
         for p in self.pipes:
             p.stream.wait_stream(cur)
             if p.pipelined and p.pending and p._ys[1 - p._cur] is None:
@@ -1197,7 +1148,7 @@ class AdaptiveGroups:
                 after = (lambda: [q.prep_done for q in self.pipes[1:]])
             else:
                 after = None
-            gens.append(p.steps(mk, after=after, prev_pipe=prevs[g] if g < len(prevs) else None))
+            gens.append(p.steps(mk, after=after, prev_pipe=prevs[g]))
         live = list(gens)
         while live:
             for gen in list(live):
@@ -1320,14 +1271,8 @@ class StaticEqPipeline:
 
     def result(self) -> Result:
         st = list(self.plan.streams)[:self.ss.n_streams]
-        return Result(y=self.y, out_offs=self.out_offs, out_lens=[s.out_len for s in st],
-                      ch=self.ss.ch, frame_base=[s.frame_base for s in st],
-                      n_frames=[s.n_frames for s in st],
-                      first_start=[s.first_start for s in st], hop=self.hop,
-                      chunk_peaks=self.peaks, chunk_base=[s.chunk_base for s in st],
-                      n_chunks=[s.n_chunks for s in st],
-                      extra=dict(n_fft=self.n_fft, norm="eps", limit=None,
-                                 limiter_applied=False, out_begin=[s.out_begin for s in st]))
+        return _result(self, st, [s.out_len for s in st],
+                       dict(norm="eps", limit=None, limiter_applied=False))
 
 
 def scale_copy(src, scale: float):
