@@ -546,7 +546,9 @@ int tomatis_an_frame_median(const float* spec, int32_t n_frames, int32_t n_bins,
 /* Per-frame band energies of rfft(win * power_mono(x)) for stereo x
  * (stft_band_tilt, calibrate_to_baseline_v2.py:17-31): out[f][0] = sum of the
  * float32 power re^2+im^2 over bins [lo0, lo1), out[f][1] over [hi0, hi1).
- * Frames and n_fft as tomatis_an_spectra. */
+ * The two ranges are independent: they may overlap, touch or be empty (sum 0),
+ * 0 <= lo0 <= lo1 <= n_fft/2+1 and likewise hi.  Frames and n_fft as
+ * tomatis_an_spectra. */
 int tomatis_an_band_energy(const float* x, int64_t n, int32_t n_fft, int32_t hop,
                            int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1,
                            const float* win, float* out, void* hip_stream);

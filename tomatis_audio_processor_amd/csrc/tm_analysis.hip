@@ -412,7 +412,9 @@ __global__ __launch_bounds__(kT) void k_an_spec_pair(SpecArgs A) {
 
 // BAND (stft_band_tilt, calibrate_to_baseline_v2.py:17-31): per frame of the
 // pair the float32 power re^2 + im^2 of rfft(win * power_mono) summed over two
-// bin ranges; workgroup per frame pair as k_an_spec_pair, block reduction.
+// bin ranges, each on its own (the reference takes any two masks: the ranges
+// may overlap or be empty); workgroup per frame pair as k_an_spec_pair, block
+// reduction.
 template <int M, bool BLUE>
 __global__ __launch_bounds__(kT) void k_an_band_pair(SpecArgs A) {
   __shared__ float2 buf[M];
@@ -437,8 +439,14 @@ __global__ __launch_bounds__(kT) void k_an_band_pair(SpecArgs A) {
     const float2 fa = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
     const float2 fb = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
     const float pa = fa.x * fa.x + fa.y * fa.y, pb = fb.x * fb.x + fb.y * fb.y;
-    acc[hi ? 1 : 0] += pa;
-    acc[hi ? 3 : 2] += pb;
+    if (lo) {
+      acc[0] += pa;
+      acc[2] += pb;
+    }
+    if (hi) {
+      acc[1] += pa;
+      acc[3] += pb;
+    }
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -861,7 +869,6 @@ int tomatis_an_band_energy(const float* x, int64_t n, int32_t n_fft, int32_t hop
   if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
   const int nb = n_fft / 2 + 1;
   if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
-  if (lo1 > hi0 && hi1 > lo0) return TOMATIS_E_ARG;  // bands must not overlap
   if (n < n_fft) return TOMATIS_OK;
   const int64_t F = 1 + (n - n_fft) / hop;
   if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
