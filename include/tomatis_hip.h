@@ -737,6 +737,48 @@ int tomatis_align_xcorr_full(const float* c, int64_t nc, const float* b, int64_t
 int tomatis_compare_residual(const float* b, const float* c, int64_t n, float gain, double* out,
                              void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * compare_to_baseline (src/compare_to_baseline.py;
+ * tm_analysis.hip, tm_align.hip).  All buffers device-resident.
+ * ------------------------------------------------------------------------- */
+
+/* doubles of workspace of tomatis_an_spectrum_mean for n_frames frames of
+ * n_bins = n_fft / 2 + 1 bins: one row of partial sums per slab of 16 frames;
+ * 0 for a count outside [1, 2^31) or n_bins < 1. */
+int64_t tomatis_an_spectrum_mean_work_doubles(int64_t n_frames, int32_t n_bins);
+
+/* avg_spectrum_db (compare_to_baseline.py:105-122): out[k] = the mean over the
+ * F = 1 + (n - n_fft) / hop frames of 10 log10(|rfft(win * s)|^2 + 1e-12), k <
+ * n_fft / 2 + 1, as float64.  Framing, signal modes (sig_mode: TOMATIS_AN_SIG_RAW
+ * with ch 1, _POWER_MONO with ch 2), scale, win and the n_fft limits are those of
+ * tomatis_an_spectra; the value of a frame and a bin is the float32 of its
+ * TOMATIS_AN_LOGPOW kind (the reference's own precision there: with numpy 2 the
+ * rfft of a float32 frame is complex64); the two real bins, 0 and for even
+ * n_fft n_fft / 2, are float64 sums of the windowed samples rounded to float32
+ * once, since a real bin passes through zero, where the logarithm magnifies the
+ * transform's rounding.  The values are added in float64:
+ * in frame order inside slabs of 16 consecutive frames, then the slabs in
+ * ascending order, then one division by F.  The order is a constant of the
+ * source and there are no floating-point atomics: the same bits on every device
+ * and in every run.  n < n_fft: nothing is written.  work:
+ * tomatis_an_spectrum_mean_work_doubles(F, n_fft / 2 + 1) doubles. */
+int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
+                             int32_t sig_mode, float scale, const float* win, double* work,
+                             double* out, void* hip_stream);
+
+/* doubles behind out of tomatis_cmp_mono_sums: [0..2] the sums, the rest scratch */
+#define TOMATIS_MONO_SUMS_DOUBLES 3075
+
+/* The time-domain sums of compute_metrics (compare_to_baseline.py:140-146,
+ * :182-184) over n frames of the interleaved stereo float32 b and c, with mb, mc
+ * their float32 power monos sqrt(0.5 (l l + r r) + 1e-12): out[0] = sum mb^2,
+ * out[1] = sum mc^2, out[2] = sum (mb - gain mc)^2; product, difference and
+ * squares in float32, the sums in float64 in the fixed order of
+ * tomatis_compare_residual.  The host forms the RMS gain from [0] and [1] of a
+ * first call and the time SNR from [0] and [2] of a second one with that gain. */
+int tomatis_cmp_mono_sums(const float* b, const float* c, int64_t n, float gain, double* out,
+                          void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

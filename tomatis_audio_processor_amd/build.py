@@ -7,13 +7,14 @@ Eight translation units, compiled in parallel and linked into one C-ABI library:
   ``TOMATIS_TRANSFORM_SCHED`` selects another LLVM machine scheduler for
   experiments — measured within 1 % of the default);
 * ``tm_analysis.hip``  analysis spectra for the validators / calibration tools
-  (SURVEY.md §8 rows f3/f4);
+  (SURVEY.md §8 rows f3/f4), the fused mean log-power spectrum of row f8;
 * ``tm_flacenc.hip``   FLAC frames encoded on the device (row f1's egress);
 * ``tm_flacdec.hip``   FLAC frames decoded on the device (row f1's ingest);
 * ``tm_declick.hip``   the de-click stage: MAD click detector and linear
   inpainting (row f5; ``-ffp-contract=off`` like the gate unit: it is bit-exact);
 * ``tm_align.hip``     the delay estimate: power-mono envelope decimator,
-  direct cross-correlation, arg-max (row f6), the residual means of row f7;
+  direct cross-correlation, arg-max (row f6), the residual means of row f7, the
+  time-domain sums of row f8;
 * ``tm_fftcorr.hip``   the power-of-two FFT in global memory and the "full"
   correlation built on it (row f7).
 """

@@ -11,6 +11,9 @@
 //   power_mono, resample_poly(m - m.mean(), up, down)    :7-10,33-34 -> k_al_pm_sum, k_al_means,
 //                                                           k_al_envelope<., true, ., .>
 //   rms_db of power_mono(b) and of power_mono(b - g c)   :96-98   -> k_al_residual, k_al_means
+// and the time-domain sums of src/compare_to_baseline.py's compute_metrics:
+//   sum mb^2, sum mc^2, sum (mb - g mc)^2                :140-146,182-184 -> k_al_mono_sums,
+//                                                           k_al_means
 // One kernel decimates, for every ratio 1 <= up < down (48 kHz: 1 / 24, 44.1 kHz: 20 / 441,
 // 192 kHz: 1 / 96), both mean orders, stereo or 1-D input.  al_envelope launches it with
 // the sums of either order, and the three envelope entry points are argument checks in
@@ -165,6 +168,40 @@ __global__ __launch_bounds__(kT) void k_al_residual(const float* __restrict__ b,
   if (threadIdx.x == 0) {
     part[blockIdx.x] = sb;
     part[kSumGroups + blockIdx.x] = sr;
+  }
+}
+
+// compare_to_baseline.py:140-146, :182-184: part[g], part[kSumGroups + g] and
+// part[2 kSumGroups + g] = float64 sums of mb^2, mc^2 and (mb - gain mc)^2 for the float32
+// power monos mb, mc; product, difference and squares in float32 as numpy forms them
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_al_mono_sums(const float* __restrict__ b,
+                                                      const float* __restrict__ c, i64 n,
+                                                      float gain, double* __restrict__ part) {
+  __shared__ double sm[kT / 64];
+  double sb = 0.0, sc = 0.0, sr = 0.0;
+  for (i64 i = (i64)blockIdx.x * kT + threadIdx.x; i < n; i += (i64)gridDim.x * kT) {
+    float bl, br, cl, cr;
+    if constexpr (VEC) {
+      const float2 u = *reinterpret_cast<const float2*>(b + 2 * i);
+      const float2 v = *reinterpret_cast<const float2*>(c + 2 * i);
+      bl = u.x, br = u.y, cl = v.x, cr = v.y;
+    } else {
+      bl = b[2 * i], br = b[2 * i + 1], cl = c[2 * i], cr = c[2 * i + 1];
+    }
+    const float mb = power_mono(bl, br), mc = power_mono(cl, cr);
+    const float r = __fsub_rn(mb, __fmul_rn(mc, gain));
+    sb += (double)__fmul_rn(mb, mb);
+    sc += (double)__fmul_rn(mc, mc);
+    sr += (double)__fmul_rn(r, r);
+  }
+  sb = block_sum(sb, sm);
+  sc = block_sum(sc, sm);
+  sr = block_sum(sr, sm);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = sb;
+    part[kSumGroups + blockIdx.x] = sc;
+    part[2 * kSumGroups + blockIdx.x] = sr;
   }
 }
 
@@ -617,6 +654,22 @@ int tomatis_compare_residual(const float* b, const float* c, int64_t n, float ga
     hipLaunchKernelGGL(k_al_residual<false>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 2);
   hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out + 2), G, kSumGroups,
                      2, (i64)n, out);
+  return al_launch();
+}
+
+int tomatis_cmp_mono_sums(const float* b, const float* c, int64_t n, float gain, double* out,
+                          void* hs) {
+  if (!b || !c || !out || n < 1) return TOMATIS_E_ARG;
+  hipStream_t s = (hipStream_t)hs;
+  const int G = sum_groups((i64)n);
+  if (aligned(b, 8) && aligned(c, 8))
+    hipLaunchKernelGGL(k_al_mono_sums<true>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain, out + 3);
+  else
+    hipLaunchKernelGGL(k_al_mono_sums<false>, dim3(G), dim3(kT), 0, s, b, c, (i64)n, gain,
+                       out + 3);
+  // the sums themselves: k_al_means with a count of one
+  hipLaunchKernelGGL(k_al_means, dim3(1), dim3(kT), 0, s, (const double*)(out + 3), G, kSumGroups,
+                     3, (i64)1, out);
   return al_launch();
 }
 

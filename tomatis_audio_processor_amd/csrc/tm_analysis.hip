@@ -13,6 +13,9 @@
 //       stable C1/C2 frames with level >= threshold, median over frames of
 //       mean_c|Y_c| / max(mean_c|X_c|, 1e-10)  -> k_an_frame_r, k_an_select,
 //                                                 k_an_spec<RATIO>, median kernels
+//   compare_to_baseline.avg_spectrum_db        src/compare_to_baseline.py:105-122
+//       mean over frames, in float64, of 10 log10(|rfft(win * power_mono)|^2 + EPS)
+//                                              -> k_an_spec_mean, k_an_spec_mean_fold
 //
 // Frames: f = 0 .. F-1 start at f*hop, F = 1 + (n - n_fft) / hop (every frame
 // lies inside the signal, as in all three reference loops).
@@ -408,6 +411,121 @@ __global__ __launch_bounds__(kT) void k_an_spec_pair(SpecArgs A) {
       }
     }
   }
+}
+
+// Mean log-power spectrum (avg_spectrum_db, compare_to_baseline.py:105-122): the
+// LOGPOW value of k_an_spec_pair, summed over frames in float64 instead of
+// stored.  A workgroup owns kSlabPairs consecutive frame pairs (a constant of
+// the source: neither the device nor the grid changes a bit of the result) and
+// walks them in frame order; a thread keeps one float64 accumulator per bin it
+// owns (bins t, t + kT, ...: registers, the LDS holds the transform) and adds
+// frame 2g, then frame 2g + 1 where it exists.  The slab's sums go to
+// work[slab][bin]; k_an_spec_mean_fold adds the slabs in ascending order.
+// The two real-valued bins, 0 and (n even) n / 2, are plain sums of the windowed
+// samples with signs +1 and (-1)^i.  A real bin passes through zero, where its
+// logarithm turns the transform's rounding (relative to the frame's largest
+// bin) into decibels, and a positive signal such as the power mono puts n / 2
+// some 50 dB under bin 0; both are therefore summed in float64 while the frame
+// is staged (a fixed shuffle tree, then the four waves in order) and rounded to
+// float32 once.
+constexpr int kSlabPairs = 8;
+
+struct MeanArgs {
+  SpecArgs S;
+  double* work;  // [slabs][n_bins]
+};
+
+template <int SIG, int M, bool BLUE>
+__global__ __launch_bounds__(kT) void k_an_spec_mean(MeanArgs B) {
+  __shared__ float2 buf[M];
+  const SpecArgs& A = B.S;
+  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
+  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
+  const int n_pairs = (A.n_frames + 1) / 2;
+  const int g0 = blockIdx.x * kSlabPairs;
+  const int g1 = min(g0 + kSlabPairs, n_pairs);
+  __shared__ double red[kT / 64][4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double acc[kMaxUB];
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) acc[u] = 0.0;
+  for (int g = g0; g < g1; ++g) {
+    const int f0 = 2 * g, f1 = f0 + 1;
+    const bool has1 = f1 < A.n_frames;
+    const int64_t p0 = (int64_t)f0 * A.hop, p1 = (int64_t)f1 * A.hop;
+    double re[4] = {0.0, 0.0, 0.0, 0.0};  // (frame a, bin 0), (a, n/2), (b, 0), (b, n/2)
+    for (int i = threadIdx.x; i < n; i += kT) {
+      const float w = A.win[i];
+      const float a = sig_at<SIG>(A.x, p0 + i, A.sc) * w;
+      const float b = has1 ? sig_at<SIG>(A.x, p1 + i, A.sc) * w : 0.f;
+      buf[i] = make_float2(a, b);
+      const double sa = (i & 1) ? -(double)a : (double)a, sb = (i & 1) ? -(double)b : (double)b;
+      re[0] += (double)a;
+      re[1] += sa;
+      re[2] += (double)b;
+      re[3] += sb;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double v = re[j];
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) red[wv][j] = v;
+    }
+    __syncthreads();
+    lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
+#pragma unroll
+    for (int u = 0; u < kMaxUB; ++u) {
+      const int k = threadIdx.x + u * kT;
+      if (k < A.n_bins) {
+        const float2 zk = buf[k], zm = buf[mirror(k, n)];
+        float2 fa = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+        float2 fb = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+        if (k == 0 || 2 * k == n) {  // the real bins: the float64 sums, rounded once
+          const int j = k == 0 ? 0 : 1;
+          double va = 0.0, vb = 0.0;
+          for (int i = 0; i < kT / 64; ++i) {
+            va += red[i][j];
+            vb += red[i][2 + j];
+          }
+          fa = make_float2((float)va, 0.f);
+          fb = make_float2((float)vb, 0.f);
+        }
+        const float pa = fa.x * fa.x + fa.y * fa.y;
+        acc[u] += (double)(10.0f * log10f(pa + kEps));
+        if (has1) {  // an odd count's last frame has no partner: nothing is added for it
+          const float pb = fb.x * fb.x + fb.y * fb.y;
+          acc[u] += (double)(10.0f * log10f(pb + kEps));
+        }
+      }
+    }
+    __syncthreads();  // buf and red are written again for the next pair
+  }
+  double* o = B.work + (int64_t)blockIdx.x * A.n_bins;
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) {
+    const int k = threadIdx.x + u * kT;
+    if (k < A.n_bins) o[k] = acc[u];
+  }
+}
+
+// out[k] = (work[0][k] + work[1][k] + ...) / max(n_frames, 1): one chain per bin
+// in ascending slab order, its loads a batch ahead as in k_an_frame_mean
+__global__ __launch_bounds__(64) void k_an_spec_mean_fold(const double* __restrict__ work,
+                                                           int n_slabs, int n_bins, int n_frames,
+                                                           double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_bins) return;
+  constexpr int kB = 16;
+  double v[kB];
+  double s = 0.0;
+  for (int s0 = 0; s0 < n_slabs; s0 += kB) {
+#pragma unroll
+    for (int u = 0; u < kB; ++u) v[u] = work[(int64_t)min(s0 + u, n_slabs - 1) * n_bins + k];
+#pragma unroll
+    for (int u = 0; u < kB; ++u)
+      if (s0 + u < n_slabs) s += v[u];
+  }
+  out[k] = s / (double)max(n_frames, 1);
 }
 
 // BAND (stft_band_tilt, calibrate_to_baseline_v2.py:17-31): per frame of the
@@ -882,6 +1000,52 @@ int tomatis_an_band_energy(const float* x, int64_t n, int32_t n_fft, int32_t hop
     hipLaunchKernelGGL((k_an_band_pair<decltype(m)::value, decltype(b)::value>), g, dim3(kT), 0,
                        s, A);
   });
+}
+
+int64_t tomatis_an_spectrum_mean_work_doubles(int64_t n_frames, int32_t n_bins) {
+  if (n_frames < 1 || n_frames > INT32_MAX || n_bins < 1) return 0;
+  const int64_t pairs = (n_frames + 1) / 2;
+  return (pairs + kSlabPairs - 1) / kSlabPairs * (int64_t)n_bins;
+}
+
+int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
+                             int32_t sig_mode, float scale, const float* win, double* work,
+                             double* out, void* hs) {
+  if (!x || !win || !work || !out || hop < 1 || ch < 1 || n_fft < 1) return TOMATIS_E_ARG;
+  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
+  if (sig_mode == TOMATIS_AN_SIG_RAW) {
+    if (ch != 1) return TOMATIS_E_ARG;
+  } else if (sig_mode == TOMATIS_AN_SIG_POWER_MONO) {
+    if (ch != 2) return TOMATIS_E_ARG;
+  } else {
+    return TOMATIS_E_ARG;
+  }
+  if (n < n_fft) return TOMATIS_OK;
+  const int64_t F = 1 + (n - n_fft) / hop;
+  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hs;
+  const int nb = n_fft / 2 + 1;
+  MeanArgs B{{x, nullptr, win, nullptr, nullptr, nullptr, nullptr, n_fft, 0, hop, (int)F, nb,
+              scale},
+             work};
+  int rc = dft_args(n_fft, s, &B.S);
+  if (rc != TOMATIS_OK) return rc;
+  const int slabs = (int)(((F + 1) / 2 + kSlabPairs - 1) / kSlabPairs);
+  const dim3 g((unsigned)slabs);
+  const bool raw = sig_mode == TOMATIS_AN_SIG_RAW;
+  rc = dispatch_m(B.S, [&](auto m, auto b) {
+    constexpr int MM = decltype(m)::value;
+    constexpr bool BL = decltype(b)::value;
+    if (raw)
+      hipLaunchKernelGGL((k_an_spec_mean<TOMATIS_AN_SIG_RAW, MM, BL>), g, dim3(kT), 0, s, B);
+    else
+      hipLaunchKernelGGL((k_an_spec_mean<TOMATIS_AN_SIG_POWER_MONO, MM, BL>), g, dim3(kT), 0, s,
+                         B);
+  });
+  if (rc != TOMATIS_OK) return rc;
+  hipLaunchKernelGGL(k_an_spec_mean_fold, dim3((nb + 63) / 64), dim3(64), 0, s,
+                     (const double*)work, slabs, nb, (int)F, out);
+  return an_launch();
 }
 
 int tomatis_cal_gate_grid(const float* levels, int32_t n_fit, const int64_t* starts,
