@@ -416,8 +416,14 @@ class _Pipelined:
         self._ys = [self._clear_idle(self.y), self._clear_idle(out2)]
         self._pks = [self.peaks, self.peaks.new_zeros(self.peaks.shape) if self.pipelined else None]
 
+    _idle = ()   # (offset, count) output slices no kernel writes: zeroed in every buffer
+
     def _clear_idle(self, buf):
-        """Hook: prepare an output buffer this pipeline gets; returns it."""
+        """Prepare an output buffer this pipeline gets (zero the slices its
+        kernels never write); returns it."""
+        if buf is not None:
+            for o, n in self._idle:
+                buf[o:o + n].zero_()
         return buf
 
     def _on_stream(self):
@@ -629,7 +635,11 @@ class GatePipeline(_Pipelined):
                 b = dsp.std_flush_bounds(N, n_fft, hop)
                 self.bounds.append(b)
                 st.in_off, st.n, st.first_start, st.n_frames = off, N, s0, F
-                st.out_begin, st.out_len = 0, (N if F else 0)
+                # where hop does not divide n_fft / 2 the last frame can end
+                # short of N (pad_end < (n_fft / 2) % hop): the reference's
+                # 0 / (0 + 1e-12) there.  The plan covers the frames; the
+                # rest of the N samples is zeroed once per buffer (_idle)
+                st.out_begin, st.out_len = 0, (min(N, s0 + (F - 1) * hop + n_fft) if F else 0)
                 nch = max(1, len(b) - 1)
                 st.n_chunks = nch
                 st.chunk_first = b[1] if len(b) > 2 else 0
@@ -638,9 +648,15 @@ class GatePipeline(_Pipelined):
             st.in_scale, st.out_scale = 1.0, float(out_scale)
             _set_gate(st, self.Ton, self.Toff)
             streams.append(st)
-        self.y, out_offs = _alloc_out(torch, [s.out_len for s in streams], ss.ch, ss.x.device)
+        # output slices of N samples per stream (the reference schedule; a
+        # geometry's are its own out_len)
+        self.res_lens = [s.out_len if (geometry is not None or not s.n_frames) else N
+                         for s, N in zip(streams, ss.lens)]
+        self.y, out_offs = _alloc_out(torch, self.res_lens, ss.ch, ss.x.device)
         for st, o in zip(streams, out_offs):
             st.out_off = o
+        self._idle = [(o + s.out_len * ss.ch, (n - s.out_len) * ss.ch)
+                      for o, n, s in zip(out_offs, self.res_lens, streams) if n > s.out_len]
         desc = TomatisPlanDesc(n_fft=n_fft, hop=hop, ch=ss.ch, norm_mode=NORM_EPS,
                                up_delay_frames=Dk, min_hold_frames=0, xfade_frames=xf,
                                alpha_mode=1 if self.xfade else 0)
@@ -756,7 +772,7 @@ class GatePipeline(_Pipelined):
     def result(self) -> Result:
         self.flush()
         st = self.streams
-        return _result(self, st, [s.out_len for s in st],
+        return _result(self, st, list(self.res_lens),
                        dict(Ton=self.Ton, Toff=self.Toff, T=self.T, xfade_frames=self.xf,
                             up_delay_samples=self.up_delay_samples, bounds=self.bounds,
                             norm="eps", limit=PEAK_LIMIT, limiter_applied=True),
@@ -862,12 +878,6 @@ class AdaptivePipeline(_Pipelined):
         self._idle = [(o, N * ss.ch) for o, N, st in zip(out_offs, self.res_lens, streams)
                       if st.n_frames == 0 and N > 0]
         self._init_pipelined(pipelined, second_buffer, out2)
-
-    def _clear_idle(self, buf):
-        if buf is not None:
-            for o, n in self._idle:
-                buf[o:o + n].zero_()
-        return buf
 
     def run(self, marks=None, timer=None, check_device: bool = True, prev_pipe=None):
         """``timer`` (a dict) collects synchronised wall-clock phases (profiling).
