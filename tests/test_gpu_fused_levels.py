@@ -302,7 +302,7 @@ def test_gated_hovering_long_runs(opts):
     """A batch whose frames exceed slots x 4096 (SURVEY C4's 512 streams on one
     GPU are 14.4 M frames on 2048 slots; TOMATIS_DEV_SLOTS reproduces the ratio
     on 8 streams) with one stream hovering at the threshold for all 5 minutes:
-    runs stay within the chained look-back (tm_kernels.hip build_runs), the pass
+    runs stay within the chained look-back (tm_plan.cpp build_runs), the pass
     takes the fused gate with no two-pass fallback, bit-identical to the
     two-pass chain (src/process_tomatis.py:373-385 has no look-back horizon)."""
     torch, E = _engine()

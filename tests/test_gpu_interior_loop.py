@@ -4,7 +4,7 @@ chunks, stores its frames' r / states through its per-run pointers and --
 pipelined -- rescales the partner pieces that its LDS-DMA brought in.
 
 TOMATIS_DEV_SLOTS leaves one or a few run slots for the interior frames, so the
-plan cuts runs of up to 4096 frames (tm_kernels.hip build_runs): 20 to 45 s of
+plan cuts runs of up to 4096 frames (tm_plan.cpp build_runs): 20 to 45 s of
 audio against the limiter's 10 s chunks.  Loud input (sample peak 1.5: most
 chunk peaks above the 0.999 limit) gives nearly every frame of a pipelined pass
 a partner piece.  Every pipelined pass must equal an unpipelined pass over the

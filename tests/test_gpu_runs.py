@@ -2,7 +2,7 @@
 
 The host cuts every stream into interior runs (fast loop) and edge runs
 (generic loop) and sizes runs to the device's resident slots
-(tm_kernels.hip plan_build); the limiter is fused in-kernel or run as a second
+(tm_plan.cpp build_runs); the limiter is fused in-kernel or run as a second
 launch.  Every output hop block is the same frame-ordered float32 sum whatever
 the cut, so outputs, chunk peaks and states must be bitwise identical across:
 run lengths (TOMATIS_DEV_RUN_FRAMES), the interior loop on/off

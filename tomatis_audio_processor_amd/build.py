@@ -1,8 +1,11 @@
 """Build ``libtomatis_hip.so`` in-tree with hipcc for gfx950 (no cmake/ninja needed).
 
-Eight translation units, compiled in parallel and linked into one C-ABI library:
+Nine translation units, compiled in parallel and linked into one C-ABI library:
 
-* ``tm_kernels.hip``   levels, gate, limiter, plan and the ``extern "C"`` entry points;
+* ``tm_kernels.hip``   levels, gate, limiter and the ``extern "C"`` launches;
+* ``tm_plan.cpp``      the plan: stream validation, path selection, every work
+  decomposition and the device buffers it owns (host code only: no kernel, no
+  device header; ``tools/plan_check.cpp`` checks it on the CPU);
 * ``tm_transform.hip`` the fused transform kernels (FMA contraction on;
   ``TOMATIS_TRANSFORM_SCHED`` selects another LLVM machine scheduler for
   experiments — measured within 1 % of the default);
@@ -31,6 +34,7 @@ CSRC = os.path.join(HERE, "csrc")
 SCHED = os.environ.get("TOMATIS_TRANSFORM_SCHED", "")
 UNITS = {  # source -> extra flags
     "tm_kernels.hip": [],
+    "tm_plan.cpp": [],
     # FMA contraction in the transform unit only (-2 % kernel time, measured): the
     # spectral path has a 1e-4 tolerance, the level / gate unit stays
     # -ffp-contract=off for its bit-exact r
@@ -44,7 +48,8 @@ UNITS = {  # source -> extra flags
     "tm_fftcorr.hip": [],
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
-                                        "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h")] + \
+                                        "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h",
+                                        "tm_layout.h", "tm_plan.h")] + \
        [os.path.join(ROOT, "include", "tomatis_hip.h"), os.path.abspath(__file__)]
 OUT = os.path.join(HERE, "libtomatis_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -63,7 +68,7 @@ def _unit_hash(src: str, cmd) -> str:
     differs is rebuilt (flags changed, or an edit landed during a build)."""
     import hashlib
     h = hashlib.sha256(" ".join(cmd[:-3] + cmd[-1:]).encode())
-    for d in [os.path.join(CSRC, src)] + [d for d in DEPS if not d.endswith(".hip")]:
+    for d in [os.path.join(CSRC, src)] + [d for d in DEPS if os.path.basename(d) not in UNITS]:
         with open(d, "rb") as f:
             h.update(f.read())
     return h.hexdigest()

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "tm_layout.h"
+
 namespace tdsp {
 
 // ---------------------------------------------------------------------------
@@ -57,11 +59,8 @@ constexpr double ct_cos2pi(long m, long M) {
 constexpr double ct_sin2pi(long m, long M) { return ct_cos2pi(m - M / 4, M); }  // M % 4 == 0
 
 // ---------------------------------------------------------------------------
-// complex float in registers
+// complex float in registers (struct cf: tm_layout.h)
 // ---------------------------------------------------------------------------
-struct cf {
-  float x, y;
-};
 __device__ __forceinline__ cf operator+(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ cf operator-(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ cf cmul(cf a, cf w) {  // a * w

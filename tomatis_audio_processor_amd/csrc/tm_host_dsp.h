@@ -1,4 +1,4 @@
-// tm_host_dsp.h — host-side tables shared by the processor plan (tm_kernels.hip)
+// tm_host_dsp.h — host-side tables shared by the processor plan (tm_plan.cpp)
 // and the analysis spectra (tm_analysis.hip): Bluestein chirp tables for a DFT
 // of any length, and numpy's pairwise-sum tree over a frame as leaves + a
 // postfix program (the device sums leaves, one thread replays the program).

@@ -15,43 +15,21 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <complex>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "tm_common.h"
-#include "tm_host_dsp.h"
 #include "tm_fft.h"
 #include "tm_shared.h"
+#include "tm_plan.h"
 #include "tm_gate.h"
-#include "../../include/tomatis_hip.h"
 
 using namespace tdsp;
 using namespace tshared;
 using namespace tgate;
 
 namespace {
-
-constexpr int kSeg = 1024;           // gate segment length (frames)
-// xfade alpha segment length (frames): each segment's alpha recurrence is one
-// lane's latency chain (k_alpha_sync / k_alpha_prefix), so short segments, many
-// waves (C5x: 3.5 k segments of 128 frames instead of 440 of 1024)
-constexpr int kASeg = 128;
-constexpr int kLevelLds = 12288;     // floats of LDS for the levels span
-constexpr int kMaxGateStates = 65535;  // uint16 state ids (transfer tables)
-
-struct LvlBlock {     // levels work item
-  int32_t s;
-  int32_t nf;
-  int64_t k0;
-};
-struct GateSeg {      // gate segment
-  int32_t s;
-  int32_t nf;
-  int64_t k0;         // first frame (stream-local)
-};
 
 
 // ===========================================================================
@@ -180,7 +158,6 @@ __global__ __launch_bounds__(256) void k_levels(const float* __restrict__ x,
 // sequential below 8, else 8 accumulators + tree + sequential remainder), one
 // thread runs the program.
 // ---------------------------------------------------------------------------
-constexpr int kPwMaxLeaves = 2048;
 
 template <typename T>
 __device__ T pw_leaf(const float* xs, int64_t n, int ch, int64_t p0, int len, T scale) {
@@ -442,16 +419,6 @@ __global__ __launch_bounds__(256) void k_gate_resolve(const float* __restrict__ 
 // frame resolves from its segment's carry-in.  Frame indices are stream-local.
 // ---------------------------------------------------------------------------
 constexpr int kNI = INT_MIN / 4;  // "none"
-struct GSum {
-  int all_on;  // every frame on
-  int not_on;  // last not-on frame
-  int l_end;   // last frame of the leading on-run (kNI if the first frame is not on)
-  int e_int;   // last entry after the first not-on frame
-  int off;     // last off frame
-};
-struct GCarry {
-  int a, e, f;
-};
 __device__ __forceinline__ GSum gs_identity() { return GSum{1, kNI, kNI, kNI, kNI}; }
 __device__ __forceinline__ GSum gs_frame(int k, uint8_t pr) {
   if (pr & 1) return GSum{1, kNI, k, kNI, kNI};
@@ -836,19 +803,6 @@ __global__ void k_alpha_xfade(const TomatisStream* __restrict__ st, int n_stream
 // state id = (C - 1) * (mh + 1) + min(since, mh)
 // ===========================================================================
 constexpr int kMhAlphaChunks = 2048;  // alpha chunks per stream (LDS carries)
-constexpr int kMhLdsTf = 8192;        // (segment, start state) transfer entries held in LDS
-constexpr int kMhLdsSym = 4096;       // symbol words held in LDS (65536 frames)
-
-// Segment length (frames, a multiple of 16 = one symbol word): at least 256,
-// few enough segments that the (segment, start) transfer table fits in LDS and
-// the final pass's segment starts fit its 4096-entry table.  Host and device.
-__host__ __device__ inline int64_t mh_seg_len(int64_t F, int ns) {
-  int64_t seg = 256;
-  const int64_t a = (F * ns + kMhLdsTf - 1) / kMhLdsTf, b = (F + 4095) / 4096;
-  seg = a > seg ? a : seg;
-  seg = b > seg ? b : seg;
-  return (seg + 15) & ~(int64_t)15;
-}
 
 // Per bisection threshold the levels reduce to 2-bit symbols per frame
 // (bit 0: level >= t_on, bit 1: level <= t_off; NaN sets neither), 16 frames
@@ -1090,11 +1044,6 @@ __global__ __launch_bounds__(1024) void k_level_stats(const double* __restrict__
 // same way; k_minhold then finishes states / alpha from them.
 // Streams whose tables spill to the HBM workspace keep the sequential kernel.
 // ---------------------------------------------------------------------------
-struct MhBisect {
-  double lo, hi, best_T, best_diff;
-  int32_t it, done, arrive, pad;
-};
-constexpr int kMhProbes = 7;
 
 __global__ void k_mh_init(const TomatisStream* __restrict__ st, int n_streams,
                           const double* __restrict__ tlh, MhBisect* __restrict__ bs) {
@@ -1119,7 +1068,6 @@ __global__ void k_mh_init(const TomatisStream* __restrict__ st, int n_streams,
 // counter) stages the tables in LDS and runs the segment chain.  Slots 0-6:
 // the tree midpoints (then, per stream, the last probe walks the taken path);
 // slot 7: best_T, whose tables k_minhold consumes.
-constexpr int kMhSlots = kMhProbes + 1;
 
 __global__ __launch_bounds__(1024) void k_mh_probe(const double* __restrict__ levels,
                                                    const TomatisStream* __restrict__ st,
@@ -1457,11 +1405,6 @@ __global__ __launch_bounds__(1024) void k_minhold(const double* __restrict__ lev
 // ===========================================================================
 // limiter fix-up, absmax, scale, synth
 // ===========================================================================
-struct ChunkDesc {
-  int32_t s, c;
-  int64_t p0, p1;  // output-relative sample range [p0, p1)
-};
-
 // sel 0: every chunk; 1: all but the edge chunks of edge_mask; 2: only those
 __global__ __launch_bounds__(256) void k_limiter(float* __restrict__ y,
                                                  const TomatisStream* __restrict__ st,
@@ -1629,855 +1572,96 @@ __global__ __launch_bounds__(256) void k_synth(float* __restrict__ x, int64_t n,
 
 }  // namespace
 
+const double* tshared::register_fft_scales(int NR, int W) {
+  if (NR == 32) return W == 0 ? splan<32, 0>().sig : W == 1 ? splan<32, 1>().sig : splan<32, 2>().sig;
+  return W == 0 ? splan<16, 0>().sig : W == 1 ? splan<16, 1>().sig : splan<16, 2>().sig;
+}
 
 // ===========================================================================
-// Host side: plan + C ABI
+// Host side: the C ABI's launches (the plan they read: tm_plan.h / tm_plan.cpp)
 // ===========================================================================
-struct tomatis_plan_s {
-  TomatisPlanDesc d{};
-  int32_t n_streams = 0;
-  int64_t total_frames = 0;
-  int32_t total_chunks = 0;
-  int P = 0, NR = 32, SH = 0, rmax = 1;
-  bool generic = false;
-  bool fx = false;  // fused kernel runs the single-exchange FFT (tm_fft.h fftx_*)
-  bool lds = false;        // any-size path (k_stft_lds + k_ola_gather_lds)
-  float2* twL = nullptr;   // lds path: exp(-2 pi i t / N)
-  std::vector<TomatisStream> hs;
-  int lvl_nf = 0;
-  // device
-  TomatisStream* st = nullptr;
-  Run* runs = nullptr;
-  int n_runs = 0;
-  std::vector<Run> hruns;  // host copy of the runs
-  LvlBlock* lblocks = nullptr;
-  int n_lblocks = 0;
-  GateSeg* segs = nullptr;
-  int n_segs = 0;
-  int32_t* seg_first = nullptr;
-  int32_t* seg_count = nullptr;
-  GateSeg* asegs = nullptr;        // xfade alpha segments (kASeg frames)
-  int n_asegs = 0;
-  int32_t* aseg_first = nullptr;
-  int32_t* aseg_count = nullptr;
-  uint16_t* tf = nullptr;
-  uint16_t* seg_start = nullptr;
-  float* win = nullptr;
-  float* winS = nullptr;  // synthesis window x the register FFT's inverse output scales
-  float* win2 = nullptr;
-  float* winv = nullptr;
-  cf* twN = nullptr;
-  cf* twP = nullptr;
-  cf* scratch = nullptr;
-  int64_t* pos_base = nullptr;
-  int64_t total_out = 0;
-  ChunkDesc* chunks = nullptr;
-  int n_chunkdesc = 0;
-  int64_t max_chunk = 0;
-  uint16_t* mh_tf = nullptr;
-  int32_t* mh_cnt = nullptr;
-  int64_t* mh_off = nullptr;
-  uint32_t* mh_sym = nullptr;
-  int64_t* mh_soff = nullptr;
-  MhBisect* mh_bs = nullptr;  // speculative bisection state per stream
-  int mh_serial = 0;          // TOMATIS_OPT_MINHOLD_SERIAL
-  int32_t* mh_pc = nullptr;   // probe counts [stream][kMhProbes]
-  uint16_t* mh_gtf = nullptr; // probe tables [stream][kMhSlots][nseg * ns]
-  int32_t* mh_gcnt = nullptr;
-  int64_t* mh_goff = nullptr;
-  int32_t* mh_arr = nullptr;  // probe arrival counters [stream][kMhSlots]
-  int mh_parts = 1;           // workgroups per probe
-  float* gperm = nullptr;
-  int gperm_rows = 0;
-  // fused limiter
-  uint32_t* chunk_need = nullptr;
-  uint32_t* chunk_done = nullptr;
-  int64_t* chunk_rng = nullptr;
-  uint32_t* err = nullptr;
-  int fuse_span = 0;  // max runs contributing to one chunk
-  int64_t run_slots = 0;  // resident sequences of the fused kernel
-  int edge_mask = 0;      // set for one tomatis_stft_ola_limited_edges call
-  int fuse_enabled = 1;   // TOMATIS_OPT_FUSE_LIMITER
-  int lim_spin = 1 << 18; // TOMATIS_OPT_LIMITER_SPIN: fused-limiter wait bound (polls)
-  // pipelined batches (tomatis_stft_ola_gated_pipelined): per run the previous
-  // batch's blocks to rescale in the frame loop (k_r2_plan output)
-  uint32_t* xs_pieces = nullptr;
-  int xs_max_pieces = 0;
-  // in-kernel levels + gate (tomatis_stft_ola_gated): per-run carry-in
-  int32_t* gate_carry = nullptr;
-  int gate_cap = 0;
-  uint16_t* gate_tf = nullptr;     // chained runs' transfer tables [gate_cap][D + 2]
-  double* gate_acarry = nullptr;   // cross-fade: alpha before each run's first frame
-  double* gate_aout = nullptr;     // cross-fade: the caller's per-frame alpha (set_gate_alpha)
-  // the look-back the carries in gate_carry belong to (input, run layout)
-  const float* gl_x = nullptr;
-  int gl_gen = -1;
-  int runs_gen = 0;                // bumped whenever build_runs re-lays the runs
-  // run-scan gate (exclusive on/off predicates)
-  bool gate_excl = false;
-  void* gsum = nullptr;
-  void* gcarry = nullptr;
-  void* gcarry_in = nullptr;  // time shards: carry-in per stream
-  int32_t* aq = nullptr;      // xfade alpha passes: sync frame per gate segment
-  double* afin = nullptr;     //   alpha at the segment end (when synced)
-  double* acin = nullptr;     //   carry-in alpha per segment
-  // streaming levels (hop % 128 == 0): per-stream 8-block groups and leaves
-  bool leaf_path = false;
-  int64_t n_groups = 0;
-  int64_t max_groups = 0;          // most groups of one stream (k_leaves grid x)
-  int64_t* grp_base = nullptr;
-  int64_t* leaf_base = nullptr;
-  void* leaves = nullptr;
-  // levels for any n_fft (k_levels_any): numpy pairwise leaves + postfix program
-  bool lvl_any = false;
-  int2* pw_leaf = nullptr;
-  int16_t* pw_prog = nullptr;
-  int n_pw_leaf = 0, n_pw_prog = 0;
-  // any-size transform: FFT length M (= n_fft, or Bluestein's power of two)
-  int lds_M = 0;
-  bool blue = false;
-  float2* blue_b = nullptr;   // chirp exp(i pi n^2 / N), n < N
-  float2* blue_h = nullptr;   // FFT_M of the chirp filter / M
-  float2* glb_work = nullptr; // M > kLdsMaxM: per-block ping-pong buffers in HBM
-  int glb_blocks = 0;
-};
-
 namespace {
-
-int hipfail(hipError_t e) { return e == hipSuccess ? TOMATIS_OK : TOMATIS_E_HIP; }
-
-template <typename T>
-int dalloc_copy(T** dst, const std::vector<T>& v) {
-  *dst = nullptr;
-  if (v.empty()) return TOMATIS_OK;
-  if (hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T)) != hipSuccess) {
-    *dst = nullptr;
-    return TOMATIS_E_NOMEM;
-  }
-  return hipfail(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-}
-
-void dfree(void* p) {
-  if (p) (void)hipFree(p);
-}
-
 
 int launch_check() { return hipfail(hipGetLastError()); }
 
+// streaming levels: leaves of 128 samples, then every frame's r from them
+template <typename T>
+void launch_leaf_levels(const tomatis_plan_s* p, const float* x, T* r_out, hipStream_t s) {
+  const tomatis_plan_s::Levels& L = p->lvl;
+  const int ns = p->n_streams;
+  const dim3 gblk((unsigned)((L.max_groups + 3) / 4), (unsigned)ns);
+  const unsigned fblk = (unsigned)((p->total_frames + 255) / 256);
+  T* lv = reinterpret_cast<T*>(L.leaves.get());
+  if (p->d.ch == 2)
+    hipLaunchKernelGGL((k_leaves<T, 2>), gblk, dim3(256), 0, s, x, p->st.get(), ns,
+                       L.grp_base.get(), L.leaf_base.get(), L.n_groups, lv);
+  else
+    hipLaunchKernelGGL((k_leaves<T, 1>), gblk, dim3(256), 0, s, x, p->st.get(), ns,
+                       L.grp_base.get(), L.leaf_base.get(), L.n_groups, lv);
+  hipLaunchKernelGGL(k_frame_r<T>, dim3(fblk), dim3(256), 0, s, p->st.get(), ns,
+                     L.leaf_base.get(), lv, p->d.n_fft, p->d.hop, p->total_frames, r_out);
+}
+
+// run-scan gate: segment summaries, the carry scan per stream (carry_in: the
+// state before each stream's first frame, or none), every frame's state
+void launch_gate_scan(const tomatis_plan_s* p, const float* r, const GCarry* carry_in,
+                      uint8_t* states, uint16_t* rows, hipStream_t s) {
+  const tomatis_plan_s::Gate& G = p->gate;
+  const int D = p->d.up_delay_frames;
+  hipLaunchKernelGGL(k_gate_sum, dim3(G.segs.n()), dim3(256), 0, s, r, p->st.get(), G.segs.get(), D,
+                     G.gsum.get());
+  hipLaunchKernelGGL(k_gate_carry, dim3(p->n_streams), dim3(256), 0, s, G.seg_first.get(),
+                     G.seg_count.get(), D, G.gsum.get(), G.gcarry.get(), carry_in);
+  hipLaunchKernelGGL(k_gate_states, dim3(G.segs.n()), dim3(256), 0, s, r, p->st.get(), G.segs.get(),
+                     D, G.gcarry.get(), states, rows);
+}
 
 }  // namespace
 
-namespace tshared {
-// development overrides (tomatis_set_dev_option); -1 = the default
-constexpr int kDevKeys = 16;
-static int g_dev[kDevKeys] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-int dev_opt(int key, int dflt) {
-  const int v = (key > 0 && key < kDevKeys) ? g_dev[key] : -1;
-  return v < 0 ? dflt : v;
-}
-}  // namespace tshared
-
 extern "C" {
-
-int tomatis_abi_version(void) { return TOMATIS_ABI_VERSION; }
-
-const char* tomatis_status_string(int s) {
-  switch (s) {
-    case TOMATIS_OK: return "ok";
-    case TOMATIS_E_ARG: return "invalid argument";
-    case TOMATIS_E_UNSUPPORTED: return "configuration not supported by the gfx950 kernels";
-    case TOMATIS_E_HIP: return "HIP runtime error";
-    case TOMATIS_E_NOMEM: return "device allocation failed";
-    default: return "unknown status";
-  }
-}
-
-int tomatis_plan_destroy(tomatis_plan_t p) {
-  if (!p) return TOMATIS_OK;
-  void* ptrs[] = {p->st, p->runs, p->lblocks, p->segs, p->seg_first, p->seg_count, p->tf,
-                  p->asegs, p->aseg_first, p->aseg_count,
-                  p->seg_start, p->win, p->winS, p->win2, p->winv, p->twN, p->twP, p->scratch,
-                  p->pos_base, p->chunks, p->mh_tf, p->mh_cnt, p->mh_off, p->mh_sym, p->mh_soff, p->mh_bs, p->mh_pc, p->mh_gtf, p->mh_gcnt, p->mh_goff, p->mh_arr, p->gperm,
-                  p->grp_base, p->leaf_base, p->leaves, p->gsum, p->gcarry, p->gcarry_in,
-                  p->aq, p->afin, p->acin,
-                  p->chunk_need, p->chunk_done, p->chunk_rng, p->err, p->twL,
-                  p->xs_pieces, p->gate_carry,
-                  p->gate_tf, p->gate_acarry,
-                  p->pw_leaf, p->pw_prog, p->blue_b, p->blue_h, p->glb_work};
-  for (void* q : ptrs) dfree(q);
-  delete p;
-  return TOMATIS_OK;
-}
-
-int64_t tomatis_plan_total_frames(tomatis_plan_t p) { return p ? p->total_frames : -1; }
-int32_t tomatis_plan_total_chunks(tomatis_plan_t p) { return p ? p->total_chunks : -1; }
-
-// no float32 bit pattern can satisfy both gate predicates (run-scan gate valid)
-static bool gate_exclusive(const TomatisStream& S) {
-  auto in = [](uint32_t b, const uint32_t* e, int n) {
-    for (int i = 0; i < n; ++i)
-      if (e[i] == b) return true;
-    return false;
-  };
-  auto on = [&](uint32_t b) { return (b >= S.on_bits) != in(b, S.on_exc, S.n_on_exc); };
-  auto off = [&](uint32_t b) { return (b <= S.off_bits) != in(b, S.off_exc, S.n_off_exc); };
-  if (S.n_on_exc < 0 || S.n_on_exc > 4 || S.n_off_exc < 0 || S.n_off_exc > 4) return false;
-  if (S.on_bits <= S.off_bits) return false;
-  for (int i = 0; i < S.n_on_exc; ++i)
-    if (on(S.on_exc[i]) && off(S.on_exc[i])) return false;
-  for (int i = 0; i < S.n_off_exc; ++i)
-    if (on(S.off_exc[i]) && off(S.off_exc[i])) return false;
-  return true;
-}
-
-// Runs of the fused kernel (plan creation), then the fused-limiter accounting
-// that depends on them.
-static int build_runs(tomatis_plan_s* p) {
-  const TomatisPlanDesc& d = p->d;
-  const int N = d.n_fft, hop = d.hop, P = p->P;
-  const int ns = p->n_streams;
-  int rc;
-  const int64_t tf_total = std::max<int64_t>(1, p->total_frames);
-  // Runs.  Per stream, the emitted frames [e_lo, e_hi) whose run can take the
-  // fused kernel's interior loop (full frame loads back to the warm-up frames,
-  // full interior output blocks, not the stream's last frame) are cut into
-  // equal runs; the few edge frames before/after form one generic run each.
-  // One run per resident sequence slot of the fused kernel (a single wave of
-  // blocks, every wave busy to the end), at least 48 frames per interior run
-  // so the rmax-1 warm-up frames per run stay a few percent.
-  const int rmax_ = (N + hop - 1) / hop;
-  const bool fast_ok = !p->generic && P == 64 && dev_opt(TOMATIS_DEV_FAST_LOOP, 1) != 0;
-  std::vector<int64_t> e_lo(ns, 0), e_hi(ns, 0);
-  int64_t fast_total = 0, n_edge = 0;
-  for (int s = 0; s < ns; ++s) {
-    const TomatisStream& S = p->hs[s];
-    const int64_t F = S.n_frames;
-    int64_t lo = F, hi = F;
-    if (fast_ok && F > 0) {
-      auto sk = [&](int64_t k) { return S.first_start + k * hop; };
-      auto ceil_div = [](int64_t a_, int64_t b_) { return a_ >= 0 ? (a_ + b_ - 1) / b_ : -((-a_) / b_); };
-      lo = rmax_ - 1;                                                   // not an edge frame
-      lo = std::max(lo, ceil_div(S.out_begin - S.first_start, hop));     // s_k >= out_begin
-      lo = std::max(lo, ceil_div(-S.first_start, hop) + rmax_ - 1);      // warm-up frames load fully
-      // s_k + hop <= out_end, s_k + N <= n, k <= F - 2
-      hi = F - 1;
-      const int64_t out_end = S.out_begin + S.out_len;
-      auto fdiv = [](int64_t a_, int64_t b_) { return a_ >= 0 ? a_ / b_ : -((-a_ + b_ - 1) / b_); };
-      hi = std::min(hi, fdiv(out_end - hop - S.first_start, hop) + 1);
-      hi = std::min(hi, fdiv(S.n - N - S.first_start, hop) + 1);
-      lo = std::max<int64_t>(0, lo);
-      if (hi - lo < 48) lo = hi = F;  // too short: all generic
-      else {
-        (void)sk;
-        n_edge += (lo > 0) + (hi < F);
-      }
-    }
-    e_lo[s] = lo;
-    e_hi[s] = hi;
-    fast_total += hi - lo;
-  }
-  // resident sequence slots of the fused kernel
-  int64_t slots;
-  {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    slots = (int64_t)std::max(1, ncu) * (p->generic ? 8 : transform_slots_per_cu(P, p->NR));
-    const int dslots = dev_opt(TOMATIS_DEV_SLOTS, 0);  // tests: long runs on small inputs
-    if (dslots > 0) slots = dslots;
-  }
-  p->run_slots = slots;
-  // Runs the in-kernel gate may take (tomatis_stft_ola_gated: standard mode at
-  // n_fft 2048) are at most kGateLookbackMax frames, so every run's look-back
-  // can chain to its predecessor's carry (k_gate_carry): a batch larger than
-  // slots x kGateLookbackMax frames gets more rounds of runs instead of longer
-  // runs, and a stream hovering inside the hysteresis band never sends the
-  // pass back to the two-pass chain (src/process_tomatis.py:373-385 has no
-  // horizon either)
-  const bool gate_runs = d.alpha_mode == 0 && N == 2048 && P == 64 && !p->generic && !p->lds;
-  // rounds: the runs fill the slots this many times over, in stream/position
-  // order, so (in-order dispatch) early streams and chunks complete while later
-  // runs still compute, and their limiter rescale overlaps that compute
-  // (adaptive: every stream is one limiter chunk, measured 1.4 ms faster on C3
-  // with 2 rounds; standard 10 s chunks gain nothing and pay warm-up frames)
-  int rounds = std::max(1, dev_opt(TOMATIS_DEV_RUN_ROUNDS, (d.alpha_mode == 2 && ns > 1) ? 2 : 1));
-  int T = dev_opt(TOMATIS_DEV_RUN_FRAMES, 0);
-  if (T <= 0) {
-    // generic streams and the edge runs take slots first
-    int64_t gen_frames = 0;
-    for (int s = 0; s < ns; ++s)
-      if (e_lo[s] == e_hi[s]) gen_frames += p->hs[s].n_frames;
-    const int64_t work = fast_total + gen_frames;
-    if (gate_runs) {  // enough rounds that runs stay within the chained look-back
-      const int64_t per_round = std::max<int64_t>(1, slots - n_edge) * (int64_t)(kGateLookbackMax - 64);
-      rounds = (int)std::max<int64_t>(rounds, (work + per_round - 1) / per_round);
-    }
-    const int64_t avail = std::max<int64_t>(1, rounds * slots - n_edge);
-    T = (int)std::max<int64_t>(rounds > 1 ? 32 : 48, (work + avail - 1) / avail);
-    auto count = [&](int64_t t) {
-      int64_t c = n_edge;
-      for (int s = 0; s < ns; ++s) {
-        const int64_t len = (e_lo[s] == e_hi[s]) ? p->hs[s].n_frames : e_hi[s] - e_lo[s];
-        c += (len + t - 1) / t;
-      }
-      return c;
-    };
-    while (count(T) > rounds * slots && T < tf_total) T += std::max(1, T / 64);
-  }
-  T = std::min(T, 1 << 20);  // interior buffer resources stay far below 4 GB
-  if (gate_runs) T = std::min(T, kGateLookbackMax);
-  std::vector<Run> runs;
-  auto add_runs = [&](int s, int64_t a0, int64_t a1, int32_t flags) {
-    // equal cuts of [a0, a1) into ceil(len / T) runs
-    const int64_t len = a1 - a0;
-    if (len <= 0) return;
-    const int64_t nr = (len + T - 1) / T;
-    for (int64_t j = 0; j < nr; ++j) {
-      Run r;
-      r.s = s;
-      r.ka = a0 + len * j / nr;
-      r.kb = a0 + len * (j + 1) / nr;
-      r.last = flags | ((r.kb == p->hs[s].n_frames) ? 1 : 0);
-      runs.push_back(r);
-    }
-  };
-  for (int s = 0; s < ns; ++s) {
-    const int64_t F = p->hs[s].n_frames;
-    if (e_lo[s] == e_hi[s]) {
-      add_runs(s, 0, F, 0);
-      continue;
-    }
-    if (e_lo[s] > 0) add_runs(s, 0, e_lo[s], 0);
-    add_runs(s, e_lo[s], e_hi[s], kRunInterior);
-    if (e_hi[s] < F) add_runs(s, e_hi[s], F, 0);
-  }
-  p->n_runs = (int)runs.size();
-  dfree(p->runs);
-  p->runs = nullptr;
-  if ((rc = dalloc_copy(&p->runs, runs))) return rc;
-  p->hruns = runs;
-  ++p->runs_gen;  // carries of an earlier look-back no longer match these runs
-  return TOMATIS_OK;
-}
-
-// Fused-limiter accounting over the plan's runs: flushes expected per chunk
-// (host mirror of the kernel's frame-indexed chunk walk) and the largest run
-// span of a chunk.
-static int limiter_accounting(tomatis_plan_s* p) {
-  if (p->generic || p->total_chunks <= 0) return TOMATIS_OK;
-  const int HOP = p->d.hop, wpr = p->P / 64;
-  const std::vector<Run>& runs = p->hruns;
-  int rc;
-  std::vector<uint32_t> need(p->total_chunks, 0);
-  std::vector<int32_t> first_run(p->total_chunks, -1), last_run(p->total_chunks, -1);
-  for (int ri = 0; ri < (int)runs.size(); ++ri) {
-    const Run& R = runs[ri];
-    const TomatisStream& S = p->hs[R.s];
-    const int64_t s_ka = S.first_start + R.ka * HOP;
-    int cid = 0;
-    if (S.n_chunks > 1 && s_ka >= S.chunk_first)
-      cid = (int)std::min<int64_t>(1 + (s_ka - S.chunk_first) / S.chunk_len, S.n_chunks - 1);
-    int64_t next_k = INT64_MAX;
-    if (S.n_chunks > 1 && cid < S.n_chunks - 1)
-      next_k = (S.chunk_first + (int64_t)cid * S.chunk_len - S.first_start) / HOP;
-    const int64_t step = S.n_chunks > 1 ? S.chunk_len / HOP : 0;
-    auto mark = [&](int c) {
-      const int g = S.chunk_base + c;
-      need[g] += wpr;
-      if (first_run[g] < 0) first_run[g] = ri;
-      last_run[g] = ri;
-    };
-    while (next_k < R.kb) {
-      if (next_k >= R.ka) {
-        mark(cid);
-        ++cid;
-        next_k = (cid < S.n_chunks - 1) ? next_k + step : INT64_MAX;
-      } else {
-        break;  // cannot happen: next chunk starts after the run's first frame
-      }
-    }
-    mark(cid);
-  }
-  int span = 0;
-  for (int g = 0; g < p->total_chunks; ++g)
-    if (first_run[g] >= 0) span = std::max(span, last_run[g] - first_run[g] + 1);
-  p->fuse_span = span;
-  dfree(p->chunk_need);
-  p->chunk_need = nullptr;
-  if ((rc = dalloc_copy(&p->chunk_need, need))) return rc;
-  dfree(p->xs_pieces);  // re-sized for these runs on the next pipelined batch
-  p->xs_pieces = nullptr;
-  p->xs_max_pieces = 0;
-  return TOMATIS_OK;
-}
-
-// in-place iterative radix-2 FFT in double (plan set-up: Bluestein filter)
-static int plan_build(tomatis_plan_s* p, const float* window) {
-  const TomatisPlanDesc& d = p->d;
-  const int N = d.n_fft, hop = d.hop, P = p->P;
-  int rc;
-  const int ns = p->n_streams;
-  // --- stream table ---
-  if ((rc = dalloc_copy(&p->st, p->hs))) return rc;
-  if ((rc = build_runs(p))) return rc;
-  // --- levels: any n_fft (numpy pairwise program) ---
-  // k_levels holds a block's span in LDS (f64: half as many samples); frames
-  // that do not fit, and every n_fft that is not a power of two >= 256, take
-  // k_levels_any
-  {
-    const bool pow2 = (N & (N - 1)) == 0;
-    const int cap32 = ((kLevelLds + 256) * 128) / 132 - 8;
-    const int cap64 = ((kLevelLds / 2 + 256) * 128) / 132 - 8;
-    p->lvl_any = !pow2 || N < 256 || N > cap32;
-    if (p->lvl_any || N > cap64) {
-      std::vector<int2> lv;
-      std::vector<int16_t> prog;
-      thost::pw_program(N, lv, prog);
-      if ((int)lv.size() > kPwMaxLeaves) return TOMATIS_E_UNSUPPORTED;
-      p->n_pw_leaf = (int)lv.size();
-      p->n_pw_prog = (int)prog.size();
-      if ((rc = dalloc_copy(&p->pw_leaf, lv))) return rc;
-      if ((rc = dalloc_copy(&p->pw_prog, prog))) return rc;
-    }
-  }
-  // --- levels blocks ---
-  if (!p->lvl_any) {
-    const int arr_f32 = kLevelLds + 256;  // matches k_levels<float> LDS
-    const int cap = (arr_f32 * 128) / 132 - 8;
-    p->lvl_nf = std::max(1, (cap - N) / hop + 1);
-    const int nleaf = N >> 7;
-    p->lvl_nf = std::min(p->lvl_nf, 1024 / nleaf);
-    std::vector<LvlBlock> lb;
-    for (int s = 0; s < ns; ++s) {
-      const int64_t F = p->hs[s].n_frames;
-      for (int64_t a = 0; a < F; a += p->lvl_nf) {
-        LvlBlock b;
-        b.s = s;
-        b.k0 = a;
-        b.nf = (int)std::min<int64_t>(p->lvl_nf, F - a);
-        lb.push_back(b);
-      }
-    }
-    p->n_lblocks = (int)lb.size();
-    if ((rc = dalloc_copy(&p->lblocks, lb))) return rc;
-  }
-  // --- streaming levels: leaves of 128 samples aligned to first_start ---
-  p->leaf_path = (hop % 128 == 0) && N >= 256 && N <= 4096 && (N & (N - 1)) == 0 &&
-                 (d.ch == 1 || d.ch == 2) && dev_opt(TOMATIS_DEV_LEVELS_LEGACY, 0) == 0;
-  if (p->leaf_path) {
-    std::vector<int64_t> gb(ns + 1, 0), lbase(ns + 1, 0);
-    for (int s = 0; s < ns; ++s) {
-      const int64_t F = p->hs[s].n_frames;
-      const int64_t nblk = F > 0 ? ((F - 1) * hop + N) / 128 : 0;
-      lbase[s + 1] = lbase[s] + nblk;
-      gb[s + 1] = gb[s] + (nblk + 7) / 8;
-      p->max_groups = std::max<int64_t>(p->max_groups, (nblk + 7) / 8);
-    }
-    p->n_groups = gb[ns];
-    if ((rc = dalloc_copy(&p->grp_base, gb))) return rc;
-    if ((rc = dalloc_copy(&p->leaf_base, lbase))) return rc;
-    if (hipMalloc(&p->leaves, (size_t)std::max<int64_t>(1, lbase[ns]) * sizeof(double)))
-      return TOMATIS_E_NOMEM;
-  }
-  // --- gate segments ---
-  {
-    std::vector<GateSeg> sg;
-    std::vector<int32_t> first(ns), count(ns);
-    auto segment = [&](int len) {
-      sg.clear();
-      for (int s = 0; s < ns; ++s) {
-        const int64_t F = p->hs[s].n_frames;
-        first[s] = (int32_t)sg.size();
-        for (int64_t a = 0; a < F; a += len) {
-          GateSeg g;
-          g.s = s;
-          g.k0 = a;
-          g.nf = (int)std::min<int64_t>(len, F - a);
-          sg.push_back(g);
-        }
-        count[s] = (int32_t)sg.size() - first[s];
-      }
-    };
-    if (d.alpha_mode == 1) {
-      segment(kASeg);
-      p->n_asegs = (int)sg.size();
-      if ((rc = dalloc_copy(&p->asegs, sg))) return rc;
-      if ((rc = dalloc_copy(&p->aseg_first, first))) return rc;
-      if ((rc = dalloc_copy(&p->aseg_count, count))) return rc;
-    }
-    segment(kSeg);
-    p->n_segs = (int)sg.size();
-    if ((rc = dalloc_copy(&p->segs, sg))) return rc;
-    p->gate_excl = dev_opt(TOMATIS_DEV_GATE_TF, 0) == 0;
-    for (int s = 0; s < ns; ++s) p->gate_excl = p->gate_excl && gate_exclusive(p->hs[s]);
-    if (p->n_segs > 0) {
-      if (hipMalloc(&p->gsum, (size_t)p->n_segs * 5 * sizeof(int))) return TOMATIS_E_NOMEM;
-      if (hipMalloc(&p->gcarry, (size_t)p->n_segs * 3 * sizeof(int))) return TOMATIS_E_NOMEM;
-    }
-    if ((rc = dalloc_copy(&p->seg_first, first))) return rc;
-    if ((rc = dalloc_copy(&p->seg_count, count))) return rc;
-    const int nstate = d.up_delay_frames + 2;
-    if (p->n_segs > 0) {
-      if (hipMalloc(reinterpret_cast<void**>(&p->tf), (size_t)p->n_segs * nstate * sizeof(uint16_t)))
-        return TOMATIS_E_NOMEM;
-      if (hipMalloc(reinterpret_cast<void**>(&p->seg_start), (size_t)p->n_segs * sizeof(uint16_t)))
-        return TOMATIS_E_NOMEM;
-    }
-  }
-  // --- tables ---
-  {
-    std::vector<float> w(window, window + N), w2(N);
-    for (int i = 0; i < N; ++i) w2[i] = w[i] * w[i];
-    std::vector<float> winv(hop);
-    for (int m = 0; m < hop; ++m) {
-      // frames covering an interior position with hop-offset m, ascending frame order
-      const int Rm = (N - m + hop - 1) / hop;
-      float acc = 0.f;
-      for (int j = Rm - 1; j >= 0; --j) acc = acc + w2[m + j * hop];
-      const float den = (d.norm_mode == TOMATIS_NORM_MAX) ? std::max(acc, 1e-8f) : (acc + 1e-12f);
-      winv[m] = 1.0f / den;
-    }
-    p->rmax = (N + hop - 1) / hop;
-    if (!p->lds) {  // register kernels only (NR = 16 or 32)
-      const int NRr = p->NR;
-      // scaled-DIF output scales of the register FFT (tm_common.h): the step-2
-      // table absorbs the forward NR-point DFT's, the synthesis window the
-      // inverse's (whose inputs carry 1 / the forward's)
-      const double* sigF = NRr == 32 ? splan<32, 0>().sig : splan<16, 0>().sig;
-      const double* sigI = NRr == 32 ? splan<32, 2>().sig : splan<16, 2>().sig;
-      // n_fft 4096 single-exchange FFT (tm_fft.h fftx128_*): wave 1 (lanes >= 64)
-      // holds k2 rotated by 16 in register r: its step-2 row r twiddles
-      // k2 = (r + 16) mod 32, and both its windows carry (-1)^n2
-      const bool fx = p->fx, rot = fx && P == 128;
-      std::vector<cf> twN((size_t)NRr * P), twP(P);
-      for (int r = 0; r < NRr; ++r)
-        for (int n1 = 0; n1 < P; ++n1) {
-          const int k2 = (rot && n1 >= 64) ? (r + 16) % 32 : r;
-          const double ang = -2.0 * M_PI * (double)((int64_t)n1 * k2 % N) / (double)N;
-          twN[((size_t)(r >> 1) * P + n1) * 2 + (r & 1)] = {(float)(cos(ang) * sigF[r]),
-                                                           (float)(sin(ang) * sigF[r])};
-        }
-      std::vector<float> winS(N);
-      // single-exchange FFTs (fftx_inv / fftx128_inv): lane m's first-DFT output scale too
-      for (int t = 0; t < N; ++t) {
-        const double sgn = (rot && (t % P) >= 64 && ((t / P) & 1)) ? -1.0 : 1.0;
-        winS[t] = (float)(sgn * (double)w[t] * sigI[t / P] *
-                          (fx ? splan<32, 1>().sig[(t % P) & 31] : 1.0));
-        if (rot && sgn < 0) w[t] = -w[t];  // analysis window (w2 / winv are built above)
-      }
-      for (int m = 0; m < P; ++m) {
-        const double ang = -2.0 * M_PI * (double)m / (double)P;
-        twP[m] = {(float)cos(ang), (float)sin(ang)};
-      }
-      if ((rc = dalloc_copy(&p->winS, winS))) return rc;
-      if ((rc = dalloc_copy(&p->twN, twN))) return rc;
-      if ((rc = dalloc_copy(&p->twP, twP))) return rc;
-    }
-    if ((rc = dalloc_copy(&p->win, w))) return rc;
-    if ((rc = dalloc_copy(&p->win2, w2))) return rc;
-    if ((rc = dalloc_copy(&p->winv, winv))) return rc;
-    if (p->lds) {
-      const int M = p->lds_M;
-      std::vector<float2> tl(M);
-      for (int t = 0; t < M; ++t) {
-        const double ang = -2.0 * M_PI * (double)t / (double)M;
-        tl[t] = make_float2((float)cos(ang), (float)sin(ang));
-      }
-      if ((rc = dalloc_copy(&p->twL, tl))) return rc;
-      if (p->blue) {
-        std::vector<float2> bf, hf;
-        thost::bluestein_tables(N, M, bf, hf);
-        if ((rc = dalloc_copy(&p->blue_b, bf))) return rc;
-        if ((rc = dalloc_copy(&p->blue_h, hf))) return rc;
-      }
-      if (M > kLdsMaxM && p->total_frames > 0) {
-        const int64_t items = p->total_frames * ((d.ch + 1) / 2);
-        // one 1024-thread block per CU keeps the chip busy; each owns two
-        // M-element buffers (2 MiB at M = 131072)
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) == hipSuccess)
-          (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        p->glb_blocks = (int)std::min<int64_t>(items, std::max(1, ncu));
-        if (hipMalloc(reinterpret_cast<void**>(&p->glb_work),
-                      (size_t)p->glb_blocks * 2 * M * sizeof(float2)))
-          return TOMATIS_E_NOMEM;
-      }
-    }
-  }
-  // --- limiter chunk descriptors, output prefix ---
-  {
-    std::vector<ChunkDesc> cd;
-    std::vector<int64_t> pb(ns);
-    int64_t tot = 0, mx = 0;
-    for (int s = 0; s < ns; ++s) {
-      const TomatisStream& S = p->hs[s];
-      pb[s] = tot;
-      tot += S.out_len;
-      const int64_t ob = S.out_begin, oe = S.out_begin + S.out_len;
-      for (int c = 0; c < S.n_chunks; ++c) {
-        int64_t b0 = (c == 0) ? INT64_MIN / 4 : S.chunk_first + (int64_t)(c - 1) * S.chunk_len;
-        int64_t b1 = (c == S.n_chunks - 1) ? INT64_MAX / 4 : S.chunk_first + (int64_t)c * S.chunk_len;
-        b0 = std::max(b0, ob);
-        b1 = std::min(b1, oe);
-        if (b1 <= b0) continue;
-        ChunkDesc C;
-        C.s = s;
-        C.c = c;
-        C.p0 = b0 - ob;
-        C.p1 = b1 - ob;
-        mx = std::max(mx, b1 - b0);
-        cd.push_back(C);
-      }
-    }
-    p->n_chunkdesc = (int)cd.size();
-    p->max_chunk = mx;
-    p->total_out = tot;
-    if ((rc = dalloc_copy(&p->chunks, cd))) return rc;
-    if ((rc = dalloc_copy(&p->pos_base, pb))) return rc;
-    // fused limiter: chunk output ranges (the per-run accounting: build_runs)
-    if (!p->generic && p->total_chunks > 0) {
-      std::vector<int64_t> rng(2 * (size_t)p->total_chunks, 0);
-      for (const ChunkDesc& C : cd) {
-        rng[2 * (p->hs[C.s].chunk_base + C.c)] = C.p0;
-        rng[2 * (p->hs[C.s].chunk_base + C.c) + 1] = C.p1;
-      }
-      if ((rc = dalloc_copy(&p->chunk_rng, rng))) return rc;
-      if (hipMalloc(reinterpret_cast<void**>(&p->chunk_done), (size_t)p->total_chunks * 4))
-        return TOMATIS_E_NOMEM;
-    }
-    if ((rc = limiter_accounting(p))) return rc;
-    if (hipMalloc(reinterpret_cast<void**>(&p->err), 4)) return TOMATIS_E_NOMEM;
-    if (hipMemset(p->err, 0, 4)) return TOMATIS_E_HIP;
-  }
-  // --- generic-hop scratch ---
-  if (p->generic && p->total_frames > 0) {
-    // register generic path: cf per position (L, R); any-size path: ch floats
-    const size_t per = p->lds ? (size_t)std::max(2, (int)d.ch) * sizeof(float) : sizeof(cf);
-    if (hipMalloc(reinterpret_cast<void**>(&p->scratch), (size_t)p->total_frames * N * per))
-      return TOMATIS_E_NOMEM;
-  }
-  // --- min-hold workspace (used when a stream's tables exceed the kernel's LDS) ---
-  if (d.min_hold_frames >= 0) {
-    const int nsm = 2 * (d.min_hold_frames + 1);
-    std::vector<int64_t> off(ns + 1, 0), soff(ns + 1, 0);
-    for (int s = 0; s < ns; ++s) {
-      const int64_t F = p->hs[s].n_frames;
-      const int64_t nseg = (F + mh_seg_len(F, nsm) - 1) / mh_seg_len(F, nsm);
-      off[s + 1] = off[s] + (nseg * nsm > kMhLdsTf ? nseg * nsm : 0);
-      soff[s + 1] = soff[s] + (((F + 15) >> 4) > kMhLdsSym ? (F + 15) >> 4 : 0);
-    }
-    if ((rc = dalloc_copy(&p->mh_off, off))) return rc;
-    if ((rc = dalloc_copy(&p->mh_soff, soff))) return rc;
-    if (off[ns] > 0) {
-      if (hipMalloc(reinterpret_cast<void**>(&p->mh_tf), off[ns] * sizeof(uint16_t))) return TOMATIS_E_NOMEM;
-      if (hipMalloc(reinterpret_cast<void**>(&p->mh_cnt), off[ns] * sizeof(int32_t))) return TOMATIS_E_NOMEM;
-    }
-    if (soff[ns] > 0 &&
-        hipMalloc(reinterpret_cast<void**>(&p->mh_sym), soff[ns] * sizeof(uint32_t)))
-      return TOMATIS_E_NOMEM;
-    if (ns > 0 && off[ns] == 0 && soff[ns] == 0) {  // speculative path: tables fit
-      if (hipMalloc(reinterpret_cast<void**>(&p->mh_bs), ns * sizeof(MhBisect))) return TOMATIS_E_NOMEM;
-      if (hipMalloc(reinterpret_cast<void**>(&p->mh_pc), ns * kMhProbes * sizeof(int32_t)))
-        return TOMATIS_E_NOMEM;
-      std::vector<int64_t> goff(ns + 1, 0);
-      int max_nseg = 1;
-      for (int s = 0; s < ns; ++s) {
-        const int64_t F = p->hs[s].n_frames;
-        const int64_t nseg = F > 0 ? (F + mh_seg_len(F, nsm) - 1) / mh_seg_len(F, nsm) : 0;
-        goff[s + 1] = goff[s] + kMhSlots * nseg * nsm;
-        max_nseg = std::max(max_nseg, (int)nseg);
-      }
-      // workgroups per probe: a few segments each (one pass of the block's
-      // threads over their (segment, start) pairs), at most 8
-      p->mh_parts = std::max(1, std::min(8, (max_nseg * nsm + 767) / 768));
-      if (const int e = tshared::dev_opt(TOMATIS_DEV_MH_PARTS, 0)) p->mh_parts = std::max(1, std::min(32, e));
-      if ((rc = dalloc_copy(&p->mh_goff, goff))) return rc;
-      if (goff[ns] > 0) {
-        if (hipMalloc(reinterpret_cast<void**>(&p->mh_gtf), goff[ns] * sizeof(uint16_t))) return TOMATIS_E_NOMEM;
-        if (hipMalloc(reinterpret_cast<void**>(&p->mh_gcnt), goff[ns] * sizeof(int32_t))) return TOMATIS_E_NOMEM;
-      }
-      if (hipMalloc(reinterpret_cast<void**>(&p->mh_arr), ns * kMhSlots * sizeof(int32_t))) return TOMATIS_E_NOMEM;
-      if (hipMemset(p->mh_arr, 0, ns * kMhSlots * sizeof(int32_t))) return TOMATIS_E_HIP;
-    }
-  }
-  return TOMATIS_OK;
-}
-
-int tomatis_plan_create(tomatis_plan_t* out, const TomatisPlanDesc* desc, const float* window,
-                        TomatisStream* streams, int32_t n_streams) {
-  if (!out || !desc || !window || (!streams && n_streams > 0) || n_streams < 0) return TOMATIS_E_ARG;
-  *out = nullptr;
-  const TomatisPlanDesc d = *desc;
-  if (d.n_fft < 2 || d.n_fft > kMaxNfft) return TOMATIS_E_UNSUPPORTED;
-  if (d.ch < 1 || d.ch > kMaxCh) return TOMATIS_E_UNSUPPORTED;
-  if (d.hop < 1 || d.hop > d.n_fft) return TOMATIS_E_ARG;
-  if (d.up_delay_frames < 0 || d.up_delay_frames + 2 > kMaxGateStates) return TOMATIS_E_UNSUPPORTED;
-  if (d.min_hold_frames < 0 || 2 * (d.min_hold_frames + 1) > 65535) return TOMATIS_E_UNSUPPORTED;
-  if (d.norm_mode != TOMATIS_NORM_EPS && d.norm_mode != TOMATIS_NORM_MAX) return TOMATIS_E_ARG;
-  auto* p = new (std::nothrow) tomatis_plan_s();
-  if (!p) return TOMATIS_E_NOMEM;
-  p->d = d;
-  p->n_streams = n_streams;
-  const int N = d.n_fft, hop = d.hop;
-  // (lanes P, registers NR) per transform: 2048 = 128 x 16, 4096 = 128 x 32
-  // n_fft 2048: one wave per frame (P = 64, 32 registers, wave-local exchanges)
-  // unless TOMATIS_P64=0; otherwise two waves per frame (P = 128)
-  // register kernels: n_fft 2048 / 4096 with <= 2 channels (L + iR); every
-  // other n_fft or more channels: the any-size path (Stockham FFT of length M,
-  // Bluestein when n_fft is not a power of two)
-  p->lds = !(N == 2048 || N == 4096) || d.ch > 2 || dev_opt(TOMATIS_DEV_FORCE_LDS, 0) != 0;
-  if (p->lds) {
-    p->blue = (N & (N - 1)) != 0;
-    int M = 1;
-    while (M < (p->blue ? 2 * N - 1 : N)) M <<= 1;
-    p->lds_M = M;
-  }
-  p->P = p->lds ? 64 : ((N == 2048 && dev_opt(TOMATIS_DEV_P64, 1)) ? 64 : 128);
-  p->NR = N / p->P;
-  p->SH = (!p->lds && hop % p->P == 0) ? hop / p->P : 0;
-  p->generic = p->lds || (p->NR == 16 ? !(p->SH == 2 || p->SH == 4 || p->SH == 8)
-                                      : !(p->SH == 4 || p->SH == 8 || p->SH == 16));
-  for (int i = 0; i < n_streams && !p->generic; ++i) {
-    const TomatisStream& s = streams[i];
-    if (s.n_chunks > 1 && (((s.chunk_first - s.first_start) % hop) != 0 || (s.chunk_len % hop) != 0))
-      p->generic = true;  // chunk boundaries not on emit blocks: per-sample gather path
-  }
-  // n_fft 2048 fused kernels: the single-exchange FFT (its bin layout and scales)
-  p->fx = kFftX && !p->generic && (p->P == 64 || p->P == 128) && p->NR == 32;
-  int64_t fb = 0;
-  int32_t cb = 0;
-  for (int i = 0; i < n_streams; ++i) {
-    TomatisStream& s = streams[i];
-    bool bad = s.n < 0 || s.n_frames < 0 || s.out_len < 0 || s.n_chunks < 1 ||
-               (s.n_chunks > 1 && s.chunk_len <= 0);
-    if (!bad && s.n_frames > 0 && s.out_begin + s.out_len > s.first_start + (s.n_frames - 1) * hop + N)
-      bad = true;  // output beyond the last frame end is never produced
-    if (!bad && s.n_frames == 0 && s.out_len > 0) bad = true;
-    if (bad) {
-      delete p;
-      return TOMATIS_E_ARG;
-    }
-    s.frame_base = fb;
-    s.chunk_base = cb;
-    fb += s.n_frames;
-    cb += s.n_chunks;
-  }
-  p->total_frames = fb;
-  p->total_chunks = cb;
-  p->hs.assign(streams, streams + n_streams);
-  const int rc = plan_build(p, window);
-  if (rc != TOMATIS_OK) {
-    tomatis_plan_destroy(p);
-    return rc;
-  }
-  *out = p;
-  return TOMATIS_OK;
-}
-
-int tomatis_plan_update_streams(tomatis_plan_t p, const TomatisStream* streams, void* hs) {
-  if (!p || !streams) return TOMATIS_E_ARG;
-  for (int i = 0; i < p->n_streams; ++i) {  // geometry is fixed at plan creation
-    const TomatisStream &a = streams[i], &b = p->hs[i];
-    if (a.in_off != b.in_off || a.out_off != b.out_off || a.n != b.n ||
-        a.first_start != b.first_start || a.n_frames != b.n_frames ||
-        a.out_begin != b.out_begin || a.out_len != b.out_len || a.chunk_first != b.chunk_first ||
-        a.chunk_len != b.chunk_len || a.n_chunks != b.n_chunks)
-      return TOMATIS_E_ARG;
-  }
-  bool excl = dev_opt(TOMATIS_DEV_GATE_TF, 0) == 0;
-  for (int i = 0; i < p->n_streams; ++i) {
-    TomatisStream s = streams[i];
-    s.frame_base = p->hs[i].frame_base;
-    s.chunk_base = p->hs[i].chunk_base;
-    p->hs[i] = s;
-    excl = excl && gate_exclusive(s);
-  }
-  p->gate_excl = excl;
-  if (p->n_streams == 0) return TOMATIS_OK;
-  return hipfail(hipMemcpyAsync(p->st, p->hs.data(), p->hs.size() * sizeof(TomatisStream),
-                                hipMemcpyHostToDevice, (hipStream_t)hs));
-}
 
 int tomatis_levels(tomatis_plan_t p, const float* x, void* r_out, int32_t prec, void* hs) {
   if (!p || !x || !r_out) return TOMATIS_E_ARG;
   if (p->total_frames == 0) return TOMATIS_OK;
+  if (prec != TOMATIS_F32 && prec != TOMATIS_F64) return TOMATIS_E_ARG;
   hipStream_t s = (hipStream_t)hs;
-  const bool any = p->lvl_any || (prec == TOMATIS_F64 && p->n_pw_prog > 0);
-  if (any && (prec == TOMATIS_F32 || prec == TOMATIS_F64)) {
+  const tomatis_plan_s::Levels& L = p->lvl;
+  const int N = p->d.n_fft, hop = p->d.hop, ch = p->d.ch;
+  const bool f64 = prec == TOMATIS_F64;
+  // (the kernels are named float first, stage by stage: their order in the code object)
+  if (L.any || (f64 && L.pw_prog.n() > 0)) {
     const unsigned g = (unsigned)std::min<int64_t>(p->total_frames, 1 << 16);
-    if (g == 0) return TOMATIS_OK;
-    if (prec == TOMATIS_F32)
-      hipLaunchKernelGGL(k_levels_any<float>, dim3(g), dim3(256), 0, s, x, p->st, p->n_streams,
-                         p->d.n_fft, p->d.hop, p->d.ch, p->pw_leaf, p->n_pw_leaf, p->pw_prog,
-                         p->n_pw_prog, p->total_frames, (float*)r_out);
+    if (!f64)
+      hipLaunchKernelGGL(k_levels_any<float>, dim3(g), dim3(256), 0, s, x, p->st.get(),
+                         p->n_streams, N, hop, ch, L.pw_leaf.get(), L.pw_leaf.n(), L.pw_prog.get(),
+                         L.pw_prog.n(), p->total_frames, (float*)r_out);
     else
-      hipLaunchKernelGGL(k_levels_any<double>, dim3(g), dim3(256), 0, s, x, p->st, p->n_streams,
-                         p->d.n_fft, p->d.hop, p->d.ch, p->pw_leaf, p->n_pw_leaf, p->pw_prog,
-                         p->n_pw_prog, p->total_frames, (double*)r_out);
-    return launch_check();
-  }
-  if (p->leaf_path && (prec == TOMATIS_F32 || prec == TOMATIS_F64)) {
-    const dim3 gblk((unsigned)((p->max_groups + 3) / 4), (unsigned)p->n_streams);
-    const unsigned fblk = (unsigned)((p->total_frames + 255) / 256);
-    const int ch = p->d.ch, N = p->d.n_fft, hop = p->d.hop, ns = p->n_streams;
-    if (prec == TOMATIS_F32) {
-      float* lv = (float*)p->leaves;
-      if (ch == 2)
-        hipLaunchKernelGGL((k_leaves<float, 2>), dim3(gblk), dim3(256), 0, s, x, p->st, ns,
-                           p->grp_base, p->leaf_base, p->n_groups, lv);
-      else
-        hipLaunchKernelGGL((k_leaves<float, 1>), dim3(gblk), dim3(256), 0, s, x, p->st, ns,
-                           p->grp_base, p->leaf_base, p->n_groups, lv);
-      hipLaunchKernelGGL(k_frame_r<float>, dim3(fblk), dim3(256), 0, s, p->st, ns, p->leaf_base,
-                         lv, N, hop, p->total_frames, (float*)r_out);
-    } else {
-      double* lv = (double*)p->leaves;
-      if (ch == 2)
-        hipLaunchKernelGGL((k_leaves<double, 2>), dim3(gblk), dim3(256), 0, s, x, p->st, ns,
-                           p->grp_base, p->leaf_base, p->n_groups, lv);
-      else
-        hipLaunchKernelGGL((k_leaves<double, 1>), dim3(gblk), dim3(256), 0, s, x, p->st, ns,
-                           p->grp_base, p->leaf_base, p->n_groups, lv);
-      hipLaunchKernelGGL(k_frame_r<double>, dim3(fblk), dim3(256), 0, s, p->st, ns, p->leaf_base,
-                         lv, N, hop, p->total_frames, (double*)r_out);
-    }
-    return launch_check();
-  }
-  if (prec == TOMATIS_F32) {
-    hipLaunchKernelGGL((k_levels<float, true>), dim3(p->n_lblocks), dim3(256), 0, s, x, p->st,
-                       p->lblocks, p->d.n_fft, p->d.hop, p->d.ch, (float*)r_out);
-  } else if (prec == TOMATIS_F64) {
+      hipLaunchKernelGGL(k_levels_any<double>, dim3(g), dim3(256), 0, s, x, p->st.get(),
+                         p->n_streams, N, hop, ch, L.pw_leaf.get(), L.pw_leaf.n(), L.pw_prog.get(),
+                         L.pw_prog.n(), p->total_frames, (double*)r_out);
+  } else if (L.leaf_path) {
+    if (!f64) launch_leaf_levels(p, x, (float*)r_out, s);
+    else launch_leaf_levels(p, x, (double*)r_out, s);
+  } else if (!f64) {
+    hipLaunchKernelGGL((k_levels<float, true>), dim3(L.blocks.n()), dim3(256), 0, s, x,
+                       p->st.get(), L.blocks.get(), N, hop, ch, (float*)r_out);
+  } else {
     // f64 blocks hold half the frames: launch twice the blocks over half-size items
-    const int N = p->d.n_fft, hop = p->d.hop;
     const int cap = ((kLevelLds / 2 + 256) * 128) / 132 - 8;
     const int nf64 = std::max(1, (cap - N) / hop + 1);
-    if (nf64 < p->lvl_nf) {
-      // build a finer block list on the fly (small host work, cached per call)
-      std::vector<LvlBlock> lb;
-      for (int st = 0; st < p->n_streams; ++st) {
-        const int64_t F = p->hs[st].n_frames;
-        for (int64_t a = 0; a < F; a += nf64) {
-          LvlBlock b;
-          b.s = st;
-          b.k0 = a;
-          b.nf = (int)std::min<int64_t>(nf64, F - a);
-          lb.push_back(b);
-        }
-      }
-      LvlBlock* dlb = nullptr;
-      int rc = dalloc_copy(&dlb, lb);
-      if (rc) return rc;
-      hipLaunchKernelGGL((k_levels<double, true>), dim3((unsigned)lb.size()), dim3(256), 0, s, x,
-                         p->st, dlb, N, hop, p->d.ch, (double*)r_out);
+    // (a finer block list: built and uploaded per call, small host work)
+    const bool finer = nf64 < L.nf;
+    DevBuf<LvlBlock> fine;
+    int rc = finer ? fine.upload(level_blocks(p, nf64)) : TOMATIS_OK;
+    if (rc) return rc;
+    const DevBuf<LvlBlock>& lb = finer ? fine : L.blocks;
+    hipLaunchKernelGGL((k_levels<double, true>), dim3(lb.n()), dim3(256), 0, s, x, p->st.get(),
+                       lb.get(), N, hop, ch, (double*)r_out);
+    if (finer) {
       rc = launch_check();
-      (void)hipStreamSynchronize(s);
-      dfree(dlb);
+      (void)hipStreamSynchronize(s);  // before the list is freed
       return rc;
     }
-    hipLaunchKernelGGL((k_levels<double, true>), dim3(p->n_lblocks), dim3(256), 0, s, x, p->st,
-                       p->lblocks, p->d.n_fft, p->d.hop, p->d.ch, (double*)r_out);
-  } else {
-    return TOMATIS_E_ARG;
   }
   return launch_check();
 }
@@ -2485,66 +1669,57 @@ int tomatis_levels(tomatis_plan_t p, const float* x, void* r_out, int32_t prec, 
 int tomatis_gate_std(tomatis_plan_t p, const float* r, uint8_t* states, uint16_t* rows,
                      double* alpha_out, void* hs) {
   if (!p || !r || !states || !rows) return TOMATIS_E_ARG;
-  if (p->n_segs == 0) return TOMATIS_OK;
+  tomatis_plan_s::Gate& G = p->gate;
+  if (G.segs.n() == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
   const int D = p->d.up_delay_frames;
   const bool xf = p->d.alpha_mode == 1;
-  if (p->gate_excl) {
-    hipLaunchKernelGGL(k_gate_sum, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                       (GSum*)p->gsum);
-    hipLaunchKernelGGL(k_gate_carry, dim3(p->n_streams), dim3(256), 0, s, p->seg_first,
-                       p->seg_count, D, (const GSum*)p->gsum, (GCarry*)p->gcarry,
-                       (const GCarry*)nullptr);
-    hipLaunchKernelGGL(k_gate_states, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                       (const GCarry*)p->gcarry, states, xf ? nullptr : rows);
+  if (G.excl) {
+    launch_gate_scan(p, r, nullptr, states, xf ? nullptr : rows, s);
   } else {
-    hipLaunchKernelGGL(k_gate_tf, dim3((p->n_segs + 3) / 4), dim3(256), 0, s, r, p->st, p->segs,
-                       p->n_segs, D, p->tf);
-    hipLaunchKernelGGL(k_gate_chain, dim3((p->n_streams + 63) / 64), dim3(64), 0, s, p->st,
-                       p->n_streams, p->seg_first, p->seg_count, D + 2, p->tf, p->seg_start, 0);
-    hipLaunchKernelGGL(k_gate_resolve, dim3((p->n_segs + 3) / 4), dim3(256), 0, s, r, p->st,
-                       p->segs, p->n_segs, D, p->seg_start, states, xf ? nullptr : rows);
+    hipLaunchKernelGGL(k_gate_tf, dim3((G.segs.n() + 3) / 4), dim3(256), 0, s, r, p->st.get(),
+                       G.segs.get(), G.segs.n(), D, G.tf.get());
+    hipLaunchKernelGGL(k_gate_chain, dim3((p->n_streams + 63) / 64), dim3(64), 0, s, p->st.get(),
+                       p->n_streams, G.seg_first.get(), G.seg_count.get(), D + 2, G.tf.get(),
+                       G.seg_start.get(), 0);
+    hipLaunchKernelGGL(k_gate_resolve, dim3((G.segs.n() + 3) / 4), dim3(256), 0, s, r, p->st.get(),
+                       G.segs.get(), G.segs.n(), D, G.seg_start.get(), states, xf ? nullptr : rows);
   }
   if (xf) {
     const int nxf = p->d.xfade_frames;
     if (dev_opt(TOMATIS_DEV_ALPHA_SEQ, 0) != 0) {
-      hipLaunchKernelGGL(k_alpha_xfade, dim3((p->n_streams + 63) / 64), dim3(64), 0, s, p->st,
-                         p->n_streams, states, nxf, rows, alpha_out);
+      hipLaunchKernelGGL(k_alpha_xfade, dim3((p->n_streams + 63) / 64), dim3(64), 0, s,
+                         p->st.get(), p->n_streams, states, nxf, rows, alpha_out);
       return launch_check();
     }
-    if (p->n_asegs == 0) return launch_check();
-    if (!p->aq) {
-      const size_t na = (size_t)p->n_asegs;
-      if (hipMalloc(reinterpret_cast<void**>(&p->aq), na * sizeof(int32_t)) ||
-          hipMalloc(reinterpret_cast<void**>(&p->afin), na * sizeof(double)) ||
-          hipMalloc(reinterpret_cast<void**>(&p->acin), na * sizeof(double)))
-        return TOMATIS_E_NOMEM;
-    }
-    const unsigned gs = (unsigned)p->n_asegs;  // one wave per alpha segment
-    hipLaunchKernelGGL(k_alpha_sync, dim3(gs), dim3(64), 0, s, p->st, p->asegs, p->n_asegs, states,
-                       nxf, rows, alpha_out, p->aq, p->afin);
-    hipLaunchKernelGGL(k_alpha_chain, dim3(p->n_streams), dim3(64), 0, s, p->st,
-                       p->n_streams, p->asegs, p->aseg_first, p->aseg_count, states, nxf, p->aq,
-                       p->afin, p->acin);
-    hipLaunchKernelGGL(k_alpha_prefix, dim3(gs), dim3(64), 0, s, p->st, p->asegs, p->n_asegs,
-                       states, nxf, p->aq, p->acin, rows, alpha_out);
+    if (G.asegs.n() == 0) return launch_check();
+    if (G.aq.ensure(G.asegs.n()) || G.afin.ensure(G.asegs.n()) || G.acin.ensure(G.asegs.n()))
+      return TOMATIS_E_NOMEM;
+    const unsigned gs = (unsigned)G.asegs.n();  // one wave per alpha segment
+    hipLaunchKernelGGL(k_alpha_sync, dim3(gs), dim3(64), 0, s, p->st.get(), G.asegs.get(),
+                       G.asegs.n(), states, nxf, rows, alpha_out, G.aq.get(), G.afin.get());
+    hipLaunchKernelGGL(k_alpha_chain, dim3(p->n_streams), dim3(64), 0, s, p->st.get(),
+                       p->n_streams, G.asegs.get(), G.aseg_first.get(), G.aseg_count.get(), states,
+                       nxf, G.aq.get(), G.afin.get(), G.acin.get());
+    hipLaunchKernelGGL(k_alpha_prefix, dim3(gs), dim3(64), 0, s, p->st.get(), G.asegs.get(),
+                       G.asegs.n(), states, nxf, G.aq.get(), G.acin.get(), rows, alpha_out);
   }
   return launch_check();
 }
 
-int32_t tomatis_plan_gate_segments(tomatis_plan_t p) { return p ? p->n_segs : -1; }
-
 int tomatis_gate_segment_sums(tomatis_plan_t p, const float* r, int32_t* sums_host, void* hs) {
   if (!p || !r || !sums_host) return TOMATIS_E_ARG;
-  if (!p->gate_excl) return TOMATIS_E_UNSUPPORTED;
-  if (p->n_segs == 0) return TOMATIS_OK;
+  tomatis_plan_s::Gate& G = p->gate;
+  if (!G.excl) return TOMATIS_E_UNSUPPORTED;
+  if (G.segs.n() == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
-  hipLaunchKernelGGL(k_gate_sum, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs,
-                     p->d.up_delay_frames, (GSum*)p->gsum);
+  hipLaunchKernelGGL(k_gate_sum, dim3(G.segs.n()), dim3(256), 0, s, r, p->st.get(), G.segs.get(),
+                     p->d.up_delay_frames, G.gsum.get());
   int rc = launch_check();
   if (rc) return rc;
   static_assert(sizeof(GSum) == 5 * sizeof(int32_t), "GSum layout");
-  if (hipMemcpyAsync(sums_host, p->gsum, (size_t)p->n_segs * sizeof(GSum), hipMemcpyDeviceToHost, s))
+  if (hipMemcpyAsync(sums_host, G.gsum.get(), (size_t)G.segs.n() * sizeof(GSum),
+                     hipMemcpyDeviceToHost, s))
     return TOMATIS_E_HIP;
   return hipfail(hipStreamSynchronize(s));
 }
@@ -2552,23 +1727,16 @@ int tomatis_gate_segment_sums(tomatis_plan_t p, const float* r, int32_t* sums_ho
 int tomatis_gate_std_carry(tomatis_plan_t p, const float* r, const int32_t* carry_host,
                            uint8_t* states, uint16_t* rows, void* hs) {
   if (!p || !r || !carry_host || !states || !rows) return TOMATIS_E_ARG;
-  if (!p->gate_excl || p->d.alpha_mode != 0) return TOMATIS_E_UNSUPPORTED;
-  if (p->n_segs == 0) return TOMATIS_OK;
+  tomatis_plan_s::Gate& G = p->gate;
+  if (!G.excl || p->d.alpha_mode != 0) return TOMATIS_E_UNSUPPORTED;
+  if (G.segs.n() == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
   static_assert(sizeof(GCarry) == 3 * sizeof(int32_t), "GCarry layout");
-  if (!p->gcarry_in && hipMalloc(&p->gcarry_in, (size_t)std::max(1, p->n_streams) * sizeof(GCarry)))
-    return TOMATIS_E_NOMEM;
-  if (hipMemcpyAsync(p->gcarry_in, carry_host, (size_t)p->n_streams * sizeof(GCarry),
+  if (G.gcarry_in.ensure((size_t)std::max(1, p->n_streams))) return TOMATIS_E_NOMEM;
+  if (hipMemcpyAsync(G.gcarry_in.get(), carry_host, (size_t)p->n_streams * sizeof(GCarry),
                      hipMemcpyHostToDevice, s))
     return TOMATIS_E_HIP;
-  const int D = p->d.up_delay_frames;
-  hipLaunchKernelGGL(k_gate_sum, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                     (GSum*)p->gsum);
-  hipLaunchKernelGGL(k_gate_carry, dim3(p->n_streams), dim3(256), 0, s, p->seg_first,
-                     p->seg_count, D, (const GSum*)p->gsum, (GCarry*)p->gcarry,
-                     (const GCarry*)p->gcarry_in);
-  hipLaunchKernelGGL(k_gate_states, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                     (const GCarry*)p->gcarry, states, rows);
+  launch_gate_scan(p, r, G.gcarry_in.get(), states, rows, s);
   int rc = launch_check();
   if (rc) return rc;
   return hipfail(hipStreamSynchronize(s));  // carry_host may be reused by the caller
@@ -2577,34 +1745,29 @@ int tomatis_gate_std_carry(tomatis_plan_t p, const float* r, const int32_t* carr
 int tomatis_ts_summary(tomatis_plan_t p, const float* r, int32_t n_seg, int32_t shift,
                        int32_t* sum_out, void* hs) {
   if (!p || !r || !sum_out || n_seg < 0) return TOMATIS_E_ARG;
-  if (!p->gate_excl || p->n_streams != 1) return TOMATIS_E_UNSUPPORTED;
+  tomatis_plan_s::Gate& G = p->gate;
+  if (!G.excl || p->n_streams != 1) return TOMATIS_E_UNSUPPORTED;
   hipStream_t s = (hipStream_t)hs;
   const int D = p->d.up_delay_frames;
-  if (p->n_segs > 0)
-    hipLaunchKernelGGL(k_gate_sum, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                       (GSum*)p->gsum);
-  hipLaunchKernelGGL(k_ts_fold, dim3(1), dim3(64), 0, s, (const GSum*)p->gsum,
-                     std::min<int>(n_seg, p->n_segs), D, shift, sum_out);
+  if (G.segs.n() > 0)
+    hipLaunchKernelGGL(k_gate_sum, dim3(G.segs.n()), dim3(256), 0, s, r, p->st.get(), G.segs.get(),
+                       D, G.gsum.get());
+  hipLaunchKernelGGL(k_ts_fold, dim3(1), dim3(64), 0, s, G.gsum.get(),
+                     std::min<int>(n_seg, G.segs.n()), D, shift, sum_out);
   return launch_check();
 }
 
 int tomatis_ts_gate(tomatis_plan_t p, const float* r, const int32_t* sums_all, int32_t rank,
                     int32_t shift, uint8_t* states, uint16_t* rows, void* hs) {
   if (!p || !r || !sums_all || rank < 0 || !states || !rows) return TOMATIS_E_ARG;
-  if (!p->gate_excl || p->d.alpha_mode != 0 || p->n_streams != 1) return TOMATIS_E_UNSUPPORTED;
-  if (p->n_segs == 0) return TOMATIS_OK;
+  tomatis_plan_s::Gate& G = p->gate;
+  if (!G.excl || p->d.alpha_mode != 0 || p->n_streams != 1) return TOMATIS_E_UNSUPPORTED;
+  if (G.segs.n() == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
-  if (!p->gcarry_in && hipMalloc(&p->gcarry_in, sizeof(GCarry))) return TOMATIS_E_NOMEM;
-  const int D = p->d.up_delay_frames;
-  hipLaunchKernelGGL(k_ts_carry, dim3(1), dim3(64), 0, s, sums_all, rank, D, shift,
-                     (GCarry*)p->gcarry_in);
-  hipLaunchKernelGGL(k_gate_sum, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                     (GSum*)p->gsum);
-  hipLaunchKernelGGL(k_gate_carry, dim3(p->n_streams), dim3(256), 0, s, p->seg_first,
-                     p->seg_count, D, (const GSum*)p->gsum, (GCarry*)p->gcarry,
-                     (const GCarry*)p->gcarry_in);
-  hipLaunchKernelGGL(k_gate_states, dim3(p->n_segs), dim3(256), 0, s, r, p->st, p->segs, D,
-                     (const GCarry*)p->gcarry, states, rows);
+  if (G.gcarry_in.ensure(1)) return TOMATIS_E_NOMEM;
+  hipLaunchKernelGGL(k_ts_carry, dim3(1), dim3(64), 0, s, sums_all, rank, p->d.up_delay_frames,
+                     shift, G.gcarry_in.get());
+  launch_gate_scan(p, r, G.gcarry_in.get(), states, rows, s);
   return launch_check();
 }
 
@@ -2612,7 +1775,7 @@ int tomatis_level_stats(tomatis_plan_t p, const double* levels, double* tlh, voi
   if (!p || !levels || !tlh) return TOMATIS_E_ARG;
   if (p->n_streams == 0) return TOMATIS_OK;
   hipLaunchKernelGGL(k_level_stats, dim3(p->n_streams), dim3(1024), 0, (hipStream_t)hs, levels,
-                     p->st, tlh);
+                     p->st.get(), tlh);
   return launch_check();
 }
 
@@ -2622,25 +1785,27 @@ int tomatis_minhold_bisect(tomatis_plan_t p, const double* levels, const double*
   if (!p || !levels || !tlh || !states) return TOMATIS_E_ARG;
   if (p->n_streams == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
+  const tomatis_plan_s::MinHold& H = p->mh;
   // speculative rounds when every stream's tables fit the probe kernel's LDS
   // (no HBM workspace); TOMATIS_MH_SERIAL keeps the one-CU-per-stream loop
-  const bool spec = !p->mh_serial && p->mh_bs && p->mh_gtf;
+  const bool spec = !H.serial && H.bs.get() && H.gtf.get();
   if (spec) {
-    const int ns = p->n_streams, P = p->mh_parts, mh = p->d.min_hold_frames;
-    hipLaunchKernelGGL(k_mh_init, dim3((ns + 255) / 256), dim3(256), 0, s, p->st, ns, tlh,
-                       p->mh_bs);
+    const int ns = p->n_streams, P = H.parts, mh = p->d.min_hold_frames;
+    hipLaunchKernelGGL(k_mh_init, dim3((ns + 255) / 256), dim3(256), 0, s, p->st.get(), ns, tlh,
+                       H.bs.get());
     for (int r = 0; r < 10; ++r)  // 30 bisection steps, three per launch
-      hipLaunchKernelGGL(k_mh_probe, dim3(ns, kMhProbes, P), dim3(1024), 0, s, levels, p->st,
-                         target_c2, hyst_db, mh, p->mh_bs, p->mh_pc, p->mh_gtf, p->mh_gcnt,
-                         p->mh_goff, p->mh_arr, 0);
-    hipLaunchKernelGGL(k_mh_probe, dim3(ns, 1, P), dim3(1024), 0, s, levels, p->st, target_c2,
-                       hyst_db, mh, p->mh_bs, p->mh_pc, p->mh_gtf, p->mh_gcnt, p->mh_goff,
-                       p->mh_arr, 1);
+      hipLaunchKernelGGL(k_mh_probe, dim3(ns, kMhProbes, P), dim3(1024), 0, s, levels,
+                         p->st.get(), target_c2, hyst_db, mh, H.bs.get(), H.pc.get(), H.gtf.get(),
+                         H.gcnt.get(), H.goff.get(), H.arr.get(), 0);
+    hipLaunchKernelGGL(k_mh_probe, dim3(ns, 1, P), dim3(1024), 0, s, levels, p->st.get(),
+                       target_c2, hyst_db, mh, H.bs.get(), H.pc.get(), H.gtf.get(), H.gcnt.get(),
+                       H.goff.get(), H.arr.get(), 1);
   }
-  hipLaunchKernelGGL(k_minhold, dim3(p->n_streams), dim3(1024), 0, s, levels, p->st, tlh,
-                     target_c2, hyst_db, p->d.min_hold_frames, p->d.xfade_frames, 1, p->mh_tf,
-                     p->mh_cnt, p->mh_off, p->mh_sym, p->mh_soff, t_out, states, rows, alpha_out,
-                     spec ? p->mh_bs : nullptr, p->mh_gtf, p->mh_gcnt, p->mh_goff);
+  hipLaunchKernelGGL(k_minhold, dim3(p->n_streams), dim3(1024), 0, s, levels, p->st.get(), tlh,
+                     target_c2, hyst_db, p->d.min_hold_frames, p->d.xfade_frames, 1, H.tf.get(),
+                     H.cnt.get(), H.off.get(), H.sym.get(), H.soff.get(), t_out, states, rows,
+                     alpha_out, spec ? H.bs.get() : nullptr, H.gtf.get(), H.gcnt.get(),
+                     H.goff.get());
   return launch_check();
 }
 
@@ -2651,45 +1816,86 @@ struct GateOut {
   bool lookback_done;  // tomatis_gate_lookback ran for this input on this stream
 };
 
+// the fused kernel's arguments as the plan determines them; a call adds its
+// own (input, output, gain rows, limit, gate outputs, previous batch)
+static MainArgs main_args(const tomatis_plan_s* p) {
+  const int N = p->d.n_fft;
+  MainArgs A{};
+  A.st = p->st.get();
+  A.runs = p->runs.get();
+  A.win = p->tab.win.get();
+  A.winS = p->tab.winS.get();
+  A.win2 = p->tab.win2.get();
+  A.twN = p->tab.twN.get();
+  A.twP = p->tab.twP.get();
+  A.winv = p->tab.winv.get();
+  A.scratch = reinterpret_cast<cf*>(p->tab.scratch.get());
+  A.n_runs = p->runs.n();
+  A.hop = p->d.hop;
+  A.n_bins = A.g_nb = N / 2 + 1;
+  A.ch = p->d.ch;
+  A.norm_mode = p->d.norm_mode;
+  A.rmax = p->generic ? 1 : p->rmax;
+  A.inv_n = 1.0f / (float)N;
+  A.lds_row[1] = 1;
+  A.edge_mask = p->lim.edge_mask;
+  A.chunk_done = p->lim.done.get();
+  A.chunk_need = p->lim.need.get();
+  A.chunk_rng = p->lim.rng.get();
+  A.err = p->lim.err.get();
+  A.lim_spin = p->lim.spin;
+  A.gate_D = p->d.up_delay_frames;
+  // cross-fade gate (alpha in-kernel): the alpha lattice's frames and step
+  A.gate_xf = p->d.alpha_mode == 1 ? p->d.xfade_frames : -1;
+  A.gate_astep = A.gate_xf > 0 ? 1.0 / A.gate_xf : 1.0;
+  A.runs_prev = A.runs;  // no other previous plan: this plan's own arrays
+  A.st_prev = A.st;
+  A.chunk_rng_prev = A.chunk_rng;
+  A.n_runs_prev = A.n_runs;
+  return A;
+}
+
 // per-run carry-in state id of the fused gate (k_gate_carry)
 static int gate_lookback(tomatis_plan_s* p, const float* x, hipStream_t s) {
+  tomatis_plan_s::Gate& G = p->gate;
   const int nst = p->d.up_delay_frames + 2;
   const bool chain = nst <= kGateChainStates;
   const bool xa = p->d.alpha_mode == 1;
-  if (p->n_runs > p->gate_cap) {
-    dfree(p->gate_carry);
-    dfree(p->gate_tf);
-    dfree(p->gate_acarry);
-    p->gate_carry = nullptr;
-    p->gate_tf = nullptr;
-    p->gate_acarry = nullptr;
-    p->gate_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&p->gate_carry), (size_t)p->n_runs * sizeof(int32_t)))
-      return TOMATIS_E_NOMEM;
-    if (chain && hipMalloc(reinterpret_cast<void**>(&p->gate_tf),
-                           (size_t)p->n_runs * nst * sizeof(uint16_t)))
-      return TOMATIS_E_NOMEM;
-    if (xa && hipMalloc(reinterpret_cast<void**>(&p->gate_acarry), (size_t)p->n_runs * sizeof(double)))
-      return TOMATIS_E_NOMEM;
-    p->gate_cap = p->n_runs;
-  }
-  p->gl_x = x;
-  p->gl_gen = p->runs_gen;
-  if (p->n_runs == 0) return TOMATIS_OK;
-  MainArgs A{};
+  if (G.carry.ensure(p->runs.n()) || (chain && G.run_tf.ensure((size_t)p->runs.n() * nst)) ||
+      (xa && G.acarry.ensure(p->runs.n())))
+    return TOMATIS_E_NOMEM;
+  G.gl_x = x;
+  if (p->runs.n() == 0) return TOMATIS_OK;
+  MainArgs A = main_args(p);
   A.x = x;
-  A.st = p->st;
-  A.runs = p->runs;
-  A.n_runs = p->n_runs;
-  A.rmax = p->rmax;
-  A.hop = p->d.hop;
-  A.ch = p->d.ch;
-  A.gate_D = p->d.up_delay_frames;
-  A.gate_xf = xa ? p->d.xfade_frames : -1;
-  A.gate_astep = (xa && p->d.xfade_frames > 0) ? 1.0 / p->d.xfade_frames : 1.0;
-  launch_gate_carry(A, p->P, p->SH, p->d.ch, p->gate_carry, (chain && !xa) ? p->gate_tf : nullptr,
-                    p->gate_acarry, s);
+  launch_gate_carry(A, p->P, p->SH, p->d.ch, G.carry.get(),
+                    (chain && !xa) ? G.run_tf.get() : nullptr, G.acarry.get(), s);
   return launch_check();
+}
+
+static LdsArgs lds_args(const tomatis_plan_s* p) {
+  LdsArgs L{};
+  L.st = p->st.get();
+  L.n_streams = p->n_streams;
+  L.win = p->tab.win.get();
+  L.win2 = p->tab.win2.get();
+  L.tw = p->any.tw.get();
+  L.blue_b = p->any.blue_b.get();
+  L.blue_h = p->any.blue_h.get();
+  L.work = p->any.work.get();
+  L.M = p->any.M;
+  L.blue = p->any.blue ? 1 : 0;
+  L.work_blocks = p->any.work_blocks;
+  L.scratch = p->tab.scratch.get();
+  L.pos_base = p->pos_base.get();
+  L.total_frames = p->total_frames;
+  L.total_out = p->total_out;
+  L.n_fft = p->d.n_fft;
+  L.hop = p->d.hop;
+  L.ch = p->d.ch;
+  L.n_bins = p->d.n_fft / 2 + 1;
+  L.norm_mode = p->d.norm_mode;
+  return L;
 }
 
 // the previous batch of a pipelined call (tomatis_stft_ola_gated_pipelined)
@@ -2701,15 +1907,12 @@ struct PrevBatch {
 
 // piece lists of the pipelined partner rescale: every run's own emitted blocks
 static int xs_pieces_alloc(tomatis_plan_s* p) {
-  if (p->xs_pieces) return TOMATIS_OK;
+  if (p->pipe.pieces.get()) return TOMATIS_OK;
   int mp = 1;
   for (const Run& R : p->hruns)
     mp = std::max<int>(mp, (int)(R.kb - std::max<int64_t>(0, R.ka - (p->rmax - 1))));
-  if (hipMalloc(reinterpret_cast<void**>(&p->xs_pieces),
-                (size_t)std::max(1, p->n_runs) * 2 * (mp + 1) * sizeof(uint32_t)))
-    return TOMATIS_E_NOMEM;
-  p->xs_max_pieces = mp;
-  return TOMATIS_OK;
+  p->pipe.max_pieces = mp;
+  return p->pipe.pieces.alloc((size_t)std::max(1, p->runs.n()) * 2 * (mp + 1));
 }
 
 static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, int32_t n_rows,
@@ -2717,36 +1920,16 @@ static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, i
                          void* hs, const GateOut* gate = nullptr,
                          const PrevBatch* prev = nullptr) {
   if (!p || !x || !gains || (!rows && !gate) || !y || !peaks || n_rows < 1) return TOMATIS_E_ARG;
-  if (p->n_runs == 0) return TOMATIS_OK;
+  if (p->runs.n() == 0) return TOMATIS_OK;
   hipStream_t s = (hipStream_t)hs;
   const int N = p->d.n_fft;
   if (p->lds) {
-    LdsArgs L;
+    LdsArgs L = lds_args(p);
     L.x = x;
-    L.st = p->st;
-    L.n_streams = p->n_streams;
     L.gains = gains;
     L.rows = rows;
-    L.win = p->win;
-    L.win2 = p->win2;
-    L.tw = p->twL;
-    L.blue_b = p->blue_b;
-    L.blue_h = p->blue_h;
-    L.work = p->glb_work;
-    L.M = p->lds_M;
-    L.blue = p->blue ? 1 : 0;
-    L.work_blocks = p->glb_blocks;
-    L.scratch = reinterpret_cast<float*>(p->scratch);
     L.y = y;
     L.peaks = peaks;
-    L.pos_base = p->pos_base;
-    L.total_frames = p->total_frames;
-    L.total_out = p->total_out;
-    L.n_fft = N;
-    L.hop = p->d.hop;
-    L.ch = p->d.ch;
-    L.n_bins = N / 2 + 1;
-    L.norm_mode = p->d.norm_mode;
     if (p->total_frames > 0) {
       launch_lds_frames(L, s);
       const int rc = launch_check();
@@ -2756,40 +1939,15 @@ static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, i
     launch_lds_gather(L, s);
     return launch_check();
   }
-  if (n_rows > p->gperm_rows) {  // grows only; reuse across calls (graph-safe after first call)
-    dfree(p->gperm);
-    p->gperm = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&p->gperm), (size_t)n_rows * N * sizeof(float)))
-      return TOMATIS_E_NOMEM;
-    p->gperm_rows = n_rows;
-  }
-  MainArgs A;
+  // grows only; reuse across calls (graph-safe after first call)
+  if (p->tab.gperm.ensure((size_t)n_rows * N)) return TOMATIS_E_NOMEM;
+  MainArgs A = main_args(p);
   A.x = x;
   A.y = y;
-  A.gains = p->gperm;
+  A.gains = p->tab.gperm.get();
   A.rows = rows;
   A.peaks = peaks;
-  A.st = p->st;
-  A.runs = p->runs;
-  A.win = p->win;
-  A.winS = p->winS;
-  A.win2 = p->win2;
-  A.twN = p->twN;
-  A.twP = p->twP;
-  A.winv = p->winv;
-  A.scratch = p->scratch;
-  A.n_runs = p->n_runs;
-  A.hop = p->d.hop;
-  A.n_bins = N / 2 + 1;
-  A.ch = p->d.ch;
-  A.norm_mode = p->d.norm_mode;
-  A.rmax = p->generic ? 1 : p->rmax;
-  A.inv_n = 1.0f / (float)N;
-  A.n_rows_lds = (n_rows <= 2 && N <= 2048) ? n_rows : 0;
-  A.lds_mixed = 0;
-  A.edge_mask = p->edge_mask;
-  A.lds_row[0] = 0;
-  A.lds_row[1] = 1;
+  if (n_rows <= 2 && N <= 2048) A.n_rows_lds = n_rows;
   if (n_rows > 2 && N <= 2048 && p->d.alpha_mode != 0 && dev_opt(TOMATIS_DEV_GAIN_LDS, 1) != 0) {
     // cross-fade tables: the pure rows (alpha 0 and 1) carry most frames
     // (xfade: rows 0/1; adaptive: rows 2 and 2 + xfade_frames = n_rows - 1)
@@ -2800,75 +1958,46 @@ static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, i
       A.lds_row[1] = n_rows - 1;
     }
   }
-  {  // every row in LDS (gm 1): the kernel prologue permutes the caller's rows
-    const bool in_lds = !p->generic && !(p->P == 128 && p->NR == 32) && A.n_rows_lds == n_rows &&
-                        !A.lds_mixed;
-    A.graw = in_lds ? gains : nullptr;
-    A.g_nb = N / 2 + 1;
-    if (!in_lds) launch_gain_perm(p->P, p->NR, p->fx, gains, n_rows, N / 2 + 1, p->gperm, s);
-  }
+  // every row in LDS (gm 1): the kernel prologue permutes the caller's rows
+  if (!p->generic && !(p->P == 128 && p->NR == 32) && A.n_rows_lds == n_rows && !A.lds_mixed)
+    A.graw = gains;
+  else
+    launch_gain_perm(p->P, p->NR, p->fx, gains, n_rows, N / 2 + 1, p->tab.gperm.get(), s);
   A.limit = limit;
-  A.chunk_done = p->chunk_done;
-  A.chunk_need = p->chunk_need;
-  A.chunk_rng = p->chunk_rng;
-  A.err = p->err;
-  A.lim_spin = p->lim_spin;
-  A.prof = nullptr;
-  A.run_base = 0;
-  A.defer_self = 0;
-  A.pieces = nullptr;
-  A.max_pieces = 0;
-  A.gated = 0;
-  A.gate_D = p->d.up_delay_frames;
-  A.r_out = nullptr;
-  A.st_out = nullptr;
-  A.gcarry = nullptr;
-  A.gtf = nullptr;
-  A.gate_xf = -1;
-  A.a_out = nullptr;
-  A.gacarry = nullptr;
-  A.yprev = nullptr;
-  A.peaks_prev = nullptr;
-  A.runs_prev = p->runs;
-  A.st_prev = p->st;
-  A.chunk_rng_prev = p->chunk_rng;
-  A.n_runs_prev = p->n_runs;
   if (gate) {
     // per run: the carry-in state id and leaf window (k_gate_carry), then the
     // transform computes every frame's r and state from the input it loads
-    // (re-run a look-back made for another input or run layout: the caller's
+    // (re-run a look-back made for another input: the caller's
     // tomatis_gate_lookback must match this call, the ABI does not assume it)
-    if (!gate->lookback_done || p->n_runs > p->gate_cap || p->gl_x != x || p->gl_gen != p->runs_gen) {
+    if (!gate->lookback_done || p->gate.gl_x != x) {
       const int rc = gate_lookback(p, x, s);
       if (rc) return rc;
     }
     A.gated = 1;
     A.r_out = gate->r;
     A.st_out = gate->states;
-    A.gcarry = p->gate_carry;
-    A.gtf = (p->d.up_delay_frames + 2 <= kGateChainStates) ? p->gate_tf : nullptr;
-    if (p->d.alpha_mode == 1) {  // cross-fade (n_fft 4096): alpha in-kernel
-      A.gate_xf = p->d.xfade_frames;
-      A.gate_astep = p->d.xfade_frames > 0 ? 1.0 / p->d.xfade_frames : 1.0;
-      A.a_out = p->gate_aout;
-      A.gacarry = p->gate_acarry;
-      A.gtf = nullptr;
+    A.gcarry = p->gate.carry.get();
+    if (p->d.alpha_mode == 1) {  // cross-fade (n_fft 4096): alpha in-kernel, no chaining
+      A.a_out = p->gate.aout;
+      A.gacarry = p->gate.acarry.get();
+    } else {
+      A.gtf = p->gate.run_tf.get();  // (none when gate_D + 2 > kGateChainStates)
     }
   }
   if (limit > 0.f) {
-    if (!p->chunk_done) return TOMATIS_E_UNSUPPORTED;
+    if (!p->lim.done.get()) return TOMATIS_E_UNSUPPORTED;
     // flush counters of the in-launch limiter (a pipelined batch counts none)
-    if (!prev && hipMemsetAsync(p->chunk_done, 0, (size_t)p->total_chunks * 4, s))
+    if (!prev && hipMemsetAsync(p->lim.done.get(), 0, (size_t)p->total_chunks * 4, s))
       return TOMATIS_E_HIP;
   }
   const int nseq = 256 / p->P;
-  const int blocks = (p->n_runs + nseq - 1) / nseq;
+  const int blocks = (p->runs.n() + nseq - 1) / nseq;
   const int ch = p->d.ch;
   if (p->generic) {
     launch_frames(A, p->P, p->NR, blocks, s);
     int rc = launch_check();
     if (rc || p->total_out == 0) return rc;
-    launch_ola_gather(A, p->n_streams, p->pos_base, p->total_out, N, s);
+    launch_ola_gather(A, p->n_streams, p->pos_base.get(), p->total_out, N, s);
     return launch_check();
   }
   if (prev) {
@@ -2883,13 +2012,14 @@ static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, i
       if (rc) return rc;
       A.yprev = prev->y;
       A.peaks_prev = prev->peaks;
-      A.runs_prev = prev->plan->runs;
-      A.st_prev = prev->plan->st;
-      A.chunk_rng_prev = prev->plan->chunk_rng;
-      A.n_runs_prev = prev->plan->n_runs;
-      A.pieces = p->xs_pieces;
-      A.max_pieces = p->xs_max_pieces;
-      launch_r2_plan(A, p->xs_pieces, p->total_chunks, p->P, s);  // (zeroes this launch's peaks)
+      A.runs_prev = prev->plan->runs.get();
+      A.st_prev = prev->plan->st.get();
+      A.chunk_rng_prev = prev->plan->lim.rng.get();
+      A.n_runs_prev = prev->plan->runs.n();
+      A.pieces = p->pipe.pieces.get();
+      A.max_pieces = p->pipe.max_pieces;
+      // (zeroes this launch's peaks)
+      launch_r2_plan(A, p->pipe.pieces.get(), p->total_chunks, p->P, s);
       if ((rc = launch_check())) return rc;
     } else if (hipMemsetAsync(peaks, 0, (size_t)p->total_chunks * 4, s)) {
       return TOMATIS_E_HIP;
@@ -2901,8 +2031,9 @@ static int stft_ola_impl(tomatis_plan_t p, const float* x, const float* gains, i
     return launch_check();
   }
 #ifdef TM_PROFILE
-  static unsigned long long* prof = nullptr;
-  if (!prof) (void)hipMalloc(reinterpret_cast<void**>(&prof), 16 * sizeof(unsigned long long));
+  static DevBuf<unsigned long long>& pbuf = *new DevBuf<unsigned long long>;  // process lifetime
+  (void)pbuf.ensure(16);
+  unsigned long long* prof = pbuf.get();
   (void)hipMemsetAsync(prof, 0, 16 * sizeof(unsigned long long), s);
   A.prof = prof;
   launch_transform(A, p->P, p->NR, p->SH, ch, transform_wg(p->P, p->NR), s);
@@ -2935,19 +2066,21 @@ int tomatis_stft_ola(tomatis_plan_t p, const float* x, const float* gains, int32
 // chunks, so at most one chunk is partly dispatched while its waves wait: any
 // span up to the resident slots progresses; half of them keeps a margin.
 constexpr int kFuseMaxSpan = 64;
-static int64_t fuse_max_span(const tomatis_plan_s* p) {
-  return std::max<int64_t>(kFuseMaxSpan, p->run_slots / 2);
+static bool fused_limiter(const tomatis_plan_s* p) {
+  return !p->generic && p->lim.done.get() && p->lim.fuse_span > 0 && p->lim.fuse_enabled &&
+         p->lim.fuse_span <= std::max<int64_t>(kFuseMaxSpan, p->run_slots / 2) &&
+         dev_opt(TOMATIS_DEV_FUSE_LIMITER, 1) != 0;
 }
 
 static int limiter_launch(tomatis_plan_t p, float* y, const uint32_t* peaks, float limit,
                           int sel, int edge_mask, void* hs) {
   if (!p || !y || !peaks) return TOMATIS_E_ARG;
-  if (p->n_chunkdesc == 0) return TOMATIS_OK;
-  const int64_t per = p->max_chunk * p->d.ch;
+  if (p->lim.chunks.n() == 0) return TOMATIS_OK;
+  const int64_t per = p->lim.max_chunk * p->d.ch;
   // ~2 float4 per thread per chunk
   const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(1, (per + 2047) / 2048), 4096);
-  hipLaunchKernelGGL(k_limiter, dim3(gx, p->n_chunkdesc), dim3(256), 0, (hipStream_t)hs, y, p->st,
-                     p->chunks, peaks, limit, p->d.ch, sel, edge_mask);
+  hipLaunchKernelGGL(k_limiter, dim3(gx, p->lim.chunks.n()), dim3(256), 0, (hipStream_t)hs, y,
+                     p->st.get(), p->lim.chunks.get(), peaks, limit, p->d.ch, sel, edge_mask);
   return launch_check();
 }
 
@@ -2955,17 +2088,11 @@ int tomatis_stft_ola_limited_edges(tomatis_plan_t p, const float* x, const float
                                    int32_t n_rows, const uint16_t* rows, float* y,
                                    uint32_t* peaks, float limit, int32_t edge_mask, void* hs) {
   if (!p || !(limit > 0.f) || edge_mask < 0 || edge_mask > 3) return TOMATIS_E_ARG;
-  const bool fuse = !p->generic && p->chunk_done && p->fuse_span > 0 && p->fuse_enabled &&
-                    p->fuse_span <= fuse_max_span(p) && dev_opt(TOMATIS_DEV_FUSE_LIMITER, 1) != 0;
-  p->edge_mask = edge_mask;
-  int rc;
-  if (fuse) {
-    rc = stft_ola_impl(p, x, gains, n_rows, rows, y, peaks, limit, hs);
-  } else {
-    rc = stft_ola_impl(p, x, gains, n_rows, rows, y, peaks, 0.f, hs);
-    if (!rc) rc = limiter_launch(p, y, peaks, limit, edge_mask ? 1 : 0, edge_mask, hs);
-  }
-  p->edge_mask = 0;
+  const bool fuse = fused_limiter(p);
+  p->lim.edge_mask = edge_mask;
+  int rc = stft_ola_impl(p, x, gains, n_rows, rows, y, peaks, fuse ? limit : 0.f, hs);
+  if (!rc && !fuse) rc = limiter_launch(p, y, peaks, limit, edge_mask ? 1 : 0, edge_mask, hs);
+  p->lim.edge_mask = 0;
   return rc;
 }
 
@@ -2997,7 +2124,7 @@ static bool gated_eligible(const tomatis_plan_s* p) {
 
 int tomatis_plan_set_gate_alpha(tomatis_plan_t p, double* alpha_out) {
   if (!p) return TOMATIS_E_ARG;
-  p->gate_aout = alpha_out;
+  p->gate.aout = alpha_out;
   return TOMATIS_OK;
 }
 
@@ -3011,7 +2138,7 @@ int tomatis_gate_lookback(tomatis_plan_t p, const float* x, void* hs) {
 // alpha lattice 0, 1/xf, ..., 1 (rows 2 + m), with the caller's alpha output set
 static bool gated_rows_ok(const tomatis_plan_s* p, int32_t n_rows) {
   if (p->d.alpha_mode != 1) return n_rows == 2;
-  return p->gate_aout && n_rows >= 2 + std::max(2, p->d.xfade_frames + 1);
+  return p->gate.aout && n_rows >= 2 + std::max(2, p->d.xfade_frames + 1);
 }
 
 static int stft_ola_gated(tomatis_plan_t p, const float* x, const float* gains, int32_t n_rows,
@@ -3022,12 +2149,9 @@ static int stft_ola_gated(tomatis_plan_t p, const float* x, const float* gains, 
   if (!gated_eligible(p)) return TOMATIS_E_UNSUPPORTED;
   if (!gated_rows_ok(p, n_rows)) return TOMATIS_E_ARG;
   const GateOut g{r_out, states_out, lookback_done};
-  if (!(limit > 0.f)) return stft_ola_impl(p, x, gains, n_rows, nullptr, y, peaks, 0.f, hs, &g);
-  const bool fuse = p->chunk_done && p->fuse_span > 0 && p->fuse_enabled &&
-                    p->fuse_span <= fuse_max_span(p) && dev_opt(TOMATIS_DEV_FUSE_LIMITER, 1) != 0;
-  if (fuse) return stft_ola_impl(p, x, gains, n_rows, nullptr, y, peaks, limit, hs, &g);
-  int rc = stft_ola_impl(p, x, gains, n_rows, nullptr, y, peaks, 0.f, hs, &g);
-  if (!rc) rc = limiter_launch(p, y, peaks, limit, 0, 0, hs);
+  const bool fuse = !(limit > 0.f) || fused_limiter(p);  // (no limit: no limiter either)
+  int rc = stft_ola_impl(p, x, gains, n_rows, nullptr, y, peaks, fuse ? limit : 0.f, hs, &g);
+  if (!rc && !fuse) rc = limiter_launch(p, y, peaks, limit, 0, 0, hs);
   return rc;
 }
 
@@ -3049,7 +2173,7 @@ int tomatis_stft_ola_gated_after_lookback(tomatis_plan_t p, const float* x, cons
 static bool prev_plan_ok(const tomatis_plan_s* p, const tomatis_plan_s* q) {
   if (q == p) return true;
   return q->d.n_fft == p->d.n_fft && q->d.hop == p->d.hop && q->d.ch == p->d.ch && q->P == p->P &&
-         q->NR == p->NR && q->SH == p->SH && !q->generic && !q->lds && q->chunk_rng &&
+         q->NR == p->NR && q->SH == p->SH && !q->generic && !q->lds && q->lim.rng.get() &&
          q->total_chunks > 0;
 }
 
@@ -3063,12 +2187,12 @@ int tomatis_stft_ola_gated_pipelined_after(tomatis_plan_t p, const float* x, con
   // the kernel's partner-rescale instantiations (gated_eligible): n_fft 2048
   // interior loop, two LDS gain rows, hop <= 512; n_fft 4096, hop 1024;
   // per-chunk accounting
-  if (!gated_eligible(p) || p->total_chunks <= 0 || !p->chunk_need || p->SH > 8)
+  if (!gated_eligible(p) || p->total_chunks <= 0 || !p->lim.need.get() || p->SH > 8)
     return TOMATIS_E_UNSUPPORTED;
   if (!gated_rows_ok(p, n_rows)) return TOMATIS_E_ARG;
   // a plan without a frame launches nothing, so it has no frame loop to limit
   // prev_y in: declined before any launch (never TOMATIS_OK with prev_y unlimited)
-  if (p->n_runs == 0) return TOMATIS_E_UNSUPPORTED;
+  if (p->runs.n() == 0) return TOMATIS_E_UNSUPPORTED;
   const tomatis_plan_s* q = prev_plan ? prev_plan : p;
   if (prev_y && !prev_plan_ok(p, q)) return TOMATIS_E_UNSUPPORTED;
   const GateOut g{r_out, states_out, true};
@@ -3108,10 +2232,10 @@ int tomatis_stft_ola_pipelined_after(tomatis_plan_t p, const float* x, const flo
   const bool p64 = p->P == 64 && lds_rows;
   const bool p128 = p->P == 128 && transform_wg(p->P, p->NR) == 512;
   if (p->generic || p->lds || p->NR != 32 || p->SH > 8 || !(p64 || p128) ||
-      p->total_chunks <= 0 || !p->chunk_need)
+      p->total_chunks <= 0 || !p->lim.need.get())
     return TOMATIS_E_UNSUPPORTED;
   // (a plan without a frame: as tomatis_stft_ola_gated_pipelined_after)
-  if (p->n_runs == 0) return TOMATIS_E_UNSUPPORTED;
+  if (p->runs.n() == 0) return TOMATIS_E_UNSUPPORTED;
   const tomatis_plan_s* q = prev_plan ? prev_plan : p;
   if (prev_y && !prev_plan_ok(p, q)) return TOMATIS_E_UNSUPPORTED;
   const PrevBatch pb{prev_y, prev_peaks, q};
@@ -3132,40 +2256,17 @@ int tomatis_plan_error(tomatis_plan_t p, void* hs) {
 }
 
 int tomatis_plan_error_bits(tomatis_plan_t p, uint32_t* bits, int32_t reset, void* hs) {
-  if (!p || !p->err || !bits) return TOMATIS_E_ARG;
+  if (!p || !p->lim.err.get() || !bits) return TOMATIS_E_ARG;
   uint32_t e = 0;
-  if (hipMemcpyAsync(&e, p->err, 4, hipMemcpyDeviceToHost, (hipStream_t)hs)) return TOMATIS_E_HIP;
+  if (hipMemcpyAsync(&e, p->lim.err.get(), 4, hipMemcpyDeviceToHost, (hipStream_t)hs))
+    return TOMATIS_E_HIP;
   if (hipStreamSynchronize((hipStream_t)hs)) return TOMATIS_E_HIP;
   *bits = e;
   if (reset && e) {
-    if (hipMemsetAsync(p->err, 0, 4, (hipStream_t)hs)) return TOMATIS_E_HIP;
+    if (hipMemsetAsync(p->lim.err.get(), 0, 4, (hipStream_t)hs)) return TOMATIS_E_HIP;
     if (hipStreamSynchronize((hipStream_t)hs)) return TOMATIS_E_HIP;
   }
   return TOMATIS_OK;
-}
-
-int tomatis_plan_set_option(tomatis_plan_t p, int32_t option, int64_t value) {
-  if (!p) return TOMATIS_E_ARG;
-  switch (option) {
-    case TOMATIS_OPT_FUSE_LIMITER: p->fuse_enabled = value != 0; return TOMATIS_OK;
-    case TOMATIS_OPT_LIMITER_SPIN:
-      if (value < 0 || value > (1 << 24)) return TOMATIS_E_ARG;
-      p->lim_spin = (int)value;
-      return TOMATIS_OK;
-    case TOMATIS_OPT_MINHOLD_SERIAL: p->mh_serial = value != 0; return TOMATIS_OK;
-    default: return TOMATIS_E_ARG;
-  }
-}
-
-int tomatis_set_dev_option(int32_t key, int32_t value) {
-  if (key <= 0 || key >= tshared::kDevKeys) return TOMATIS_E_ARG;
-  tshared::g_dev[key] = value < 0 ? -1 : value;
-  return TOMATIS_OK;
-}
-
-int32_t tomatis_get_dev_option(int32_t key) {
-  if (key <= 0 || key >= tshared::kDevKeys) return -1;
-  return tshared::g_dev[key];
 }
 
 
@@ -3196,7 +2297,7 @@ int tomatis_absmax_streams(tomatis_plan_t p, const float* x, uint32_t* out, void
   const unsigned gx = (unsigned)std::max<int64_t>(
       1, std::min<int64_t>(std::max(8, 1024 / p->n_streams), (nmax + 4095) / 4096));
   hipLaunchKernelGGL(k_absmax_streams, dim3(gx, p->n_streams), dim3(256), 0, (hipStream_t)hs, x,
-                     p->st, p->d.ch, out);
+                     p->st.get(), p->d.ch, out);
   return launch_check();
 }
 

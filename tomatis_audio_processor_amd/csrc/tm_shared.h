@@ -1,27 +1,19 @@
-// tm_shared.h — types shared by the two translation units of libtomatis_hip:
-// tm_kernels.hip (levels, gate, limiter, plan, C ABI) and tm_transform.hip
-// (the fused transform kernels, compiled with the max-ILP scheduler).
+// tm_shared.h — the argument structs and launchers shared by the two device
+// units of the processor: tm_kernels.hip (levels, gate, limiter, the C ABI's
+// launches) and tm_transform.hip (the fused transform kernels).  The plain
+// types they share with the host-only plan (tm_plan.cpp) are in tm_layout.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tm_common.h"
-#include "../../include/tomatis_hip.h"
+#include "tm_layout.h"
 
 namespace tshared {
 using tdsp::cf;
 
 constexpr float kEps32 = 1e-12f;  // EPS as the reference adds it to float32 arrays
 constexpr double kEps64 = 1e-12;
-
-struct Run {          // main-kernel work item: emit frames [ka, kb) of stream s
-  int32_t s;
-  int32_t last;       // bit 0: kb is the stream's last frame + 1; bit 1: kRunInterior
-  int64_t ka, kb;
-};
-// interior run: frames [max(0, ka - rmax + 1), kb) all read full frames and every
-// emitted hop block is a full interior block (fast loop of the fused kernel)
-constexpr int32_t kRunInterior = 2;
 
 __device__ __forceinline__ int64_t floordiv(int64_t a, int64_t b) {
   int64_t q = a / b;
@@ -119,19 +111,7 @@ void launch_prev_runs(const MainArgs& A, int N, hipStream_t s);
 // alpha before each run's first frame into gacarry, no chaining)
 void launch_gate_carry(const MainArgs& A, int P, int SH, int ch, int32_t* gcarry,
                        uint16_t* gtf, double* gacarry, hipStream_t s);
-constexpr int kGateLookback = 512;       // look-back limit of a run that cannot chain
-constexpr int kGateLookbackMax = 4096;   // chained runs: frames back to the previous run's start
-constexpr int kGateChainStates = 1024;   // chaining needs gate_D + 2 <= this (transfer tables)
-constexpr int kGateChained = -2;         // k_gate_carry -> k_gate_chain marker
 
-// Any-size path (any n_fft in [2, kMaxNfft], any hop, 1..kMaxCh channels): per
-// (frame, channel pair) a Stockham FFT of length M (n_fft when it is a power
-// of two, else Bluestein's power of two >= 2 n_fft - 1) in LDS (M <= kLdsMaxM)
-// or in per-block HBM buffers, windowed frames to scratch float
-// [frame][n_fft][ch], then a per-position gather in frame order.
-constexpr int kMaxNfft = 1 << 16;
-constexpr int kMaxCh = 128;
-constexpr int kLdsMaxM = 16384;
 struct LdsArgs {
   const float* x;
   const TomatisStream* st;
@@ -155,24 +135,12 @@ struct LdsArgs {
 void launch_lds_frames(const LdsArgs& A, hipStream_t s);
 void launch_lds_gather(const LdsArgs& A, hipStream_t s);
 
-// n_fft 2048 register kernels (P = 64) run the single-exchange FFT (tm_fft.h
-// fftx_*; its bin layout in the gain rows, its output scales in winS); the
-// two-exchange form stays for n_fft 4096 and for -DTM_DEV_NOFX A/B builds
-#ifdef TM_DEV_NOFX
-constexpr bool kFftX = false;
-#else
-constexpr bool kFftX = true;
-#endif
-
 // launchers (tm_transform.hip); kernels stay private to that unit
-int transform_wg(int P, int NR);  // workgroup size of the fused kernel
-int transform_slots_per_cu(int P, int NR);  // resident sequences per CU
 void launch_transform(const MainArgs& A, int P, int NR, int SH, int ch, int wg, hipStream_t s);
 void launch_frames(const MainArgs& A, int P, int NR, int blocks, hipStream_t s);
 void launch_gain_perm(int P, int NR, bool fx, const float* gains, int n_rows, int n_bins,
                       float* out, hipStream_t s);
 void launch_ola_gather(const MainArgs& A, int n_streams, const int64_t* pos_base, int64_t total,
                        int N, hipStream_t s);
-int dev_opt(int key, int dflt);  // tomatis_set_dev_option (default when unset)
 
 }  // namespace tshared
