@@ -779,6 +779,54 @@ int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_ff
 int tomatis_cmp_mono_sums(const float* b, const float* c, int64_t n, float gain, double* out,
                           void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * Acceptance validators (src/verify_tomatis_15db_v2.py,
+ * src/validate_layer1.py; tm_analysis.hip).  x and y float32 [n][ch]
+ * interleaved, ch 1 or 2, both n frames long; frames, win and the n_fft limits
+ * as tomatis_an_spectra; one workgroup per frame and one transform of
+ * x_c + i y_c per channel.  All buffers device-resident.  Every sum below is a
+ * block reduction in a fixed order (no atomics): the same bits in every run, and
+ * the same bits from the single calls as from tomatis_an_verify_pair.
+ * ------------------------------------------------------------------------- */
+
+/* The anchored ratio rows of compute_conditional_spectrum_v2
+ * (verify_tomatis_15db_v2.py:307-354): rows[f][k] = ratio[k] / g with
+ * ratio[k] = mean_c|Y_c[k]| / max(mean_c|X_c[k]|, 1e-10) as TOMATIS_AN_RATIO
+ * forms it and g = mean(ratio[a0:a1]), float32; the row is left as ratio when
+ * the anchor range is empty (a0 == a1) or g > 0 does not hold (:326-328: the
+ * mean of an empty slice is NaN, and NaN > 0 is false).
+ * 0 <= a0 <= a1 <= n_fft/2+1.  rows: F * (n_fft/2+1) floats. */
+int tomatis_an_anchored_ratio(const float* x, const float* y, int64_t n, int32_t ch,
+                              int32_t n_fft, int32_t hop, int32_t a0, int32_t a1,
+                              const float* win, float* rows, void* hip_stream);
+
+/* The band energies of compute_tilt_index (verify_tomatis_15db_v2.py:451-470):
+ * with P_x[k] = mean_c |X_c[k]|^2 (re^2 + im^2 in float32) and P_y likewise,
+ * bands[f] = (sum P_x[lo0:lo1], sum P_x[hi0:hi1], sum P_y[lo0:lo1],
+ * sum P_y[hi0:hi1]).  The two ranges are independent and may be empty (sum 0),
+ * as in tomatis_an_band_energy.  bands: F * 4 floats. */
+int tomatis_an_pair_band_energy(const float* x, const float* y, int64_t n, int32_t ch,
+                                int32_t n_fft, int32_t hop, int32_t lo0, int32_t lo1,
+                                int32_t hi0, int32_t hi1, const float* win, float* bands,
+                                void* hip_stream);
+
+/* Both of the above from one transform per (frame, channel): sections C and D
+ * of the validator need |X_c| and |Y_c| of the same frames (:307-354 and
+ * :451-470 in one pass). */
+int tomatis_an_verify_pair(const float* x, const float* y, int64_t n, int32_t ch, int32_t n_fft,
+                           int32_t hop, int32_t a0, int32_t a1, int32_t lo0, int32_t lo1,
+                           int32_t hi0, int32_t hi1, const float* win, float* rows, float* bands,
+                           void* hip_stream);
+
+/* doubles behind out of tomatis_sum_f64: [0] the sum, the rest scratch */
+#define TOMATIS_SUM_DOUBLES 1025
+
+/* out[0] = the float64 sum of n float32 values (np.mean(y) of check_engineering,
+ * verify_tomatis_15db_v2.py:90, is out[0] / n): 1024 partial sums over a fixed
+ * grid (element i in group (i / 256) mod 1024), folded in index order; the same
+ * bits in every run and on every device.  n == 0: 0. */
+int tomatis_sum_f64(const float* x, int64_t n, double* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ OPT_MINHOLD_SERIAL = 3   # TOMATIS_OPT_MINHOLD_SERIAL
 ALIGN_MEAN_DOUBLES = 1025  # TOMATIS_ALIGN_MEAN_DOUBLES
 RESIDUAL_DOUBLES = 2050    # TOMATIS_RESIDUAL_DOUBLES
 MONO_SUMS_DOUBLES = 3075   # TOMATIS_MONO_SUMS_DOUBLES
+SUM_DOUBLES = 1025         # TOMATIS_SUM_DOUBLES
 FFT_MIN_LOG2, FFT_MAX_LOG2 = 4, 25  # TOMATIS_FFT_MIN_LOG2, TOMATIS_FFT_MAX_LOG2
 # development overrides (TOMATIS_DEV_*: tests and A/B experiments only)
 DEV_KEYS = dict(FAST_LOOP=1, RUN_ROUNDS=2, RUN_FRAMES=3, LEVELS_LEGACY=4, GATE_TF=5, MH_PARTS=6,
@@ -185,6 +186,16 @@ _SIGS = {
     "tomatis_an_spectrum_mean": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_float, _P, _P, _P, _P]),
     "tomatis_cmp_mono_sums": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P]),
+    # acceptance validators
+    "tomatis_an_anchored_ratio": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, _P, _P, _P]),
+    "tomatis_an_pair_band_energy": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                              _P]),
+    "tomatis_an_verify_pair": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, _P, _P, _P, _P]),
+    "tomatis_sum_f64": (C.c_int, [_P, C.c_int64, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

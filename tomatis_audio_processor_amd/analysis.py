@@ -8,6 +8,10 @@ the reference functions:
   find_stable_frames            src/validate_layer1.py:245-258 (host: list logic)
   compute_conditional_spectrum  src/validate_layer1.py:261-389
 
+and, below them, the device pieces the two acceptance validators share
+(validate_layer1.py, verify_tomatis_15db_v2.py; row f9): the padded level grid,
+the gate scan, the anchored ratio rows and band energies, peak and float64 sum.
+
 Everything per frame or per sample runs in ``libtomatis_hip.so``
 (``tm_analysis.hip``): framing, power-mono premix, window, real FFT (two real
 frames per complex FFT), |X| / log-power / Y-over-X ratios, the per-frame
@@ -183,6 +187,20 @@ def stft_logpower_median(x_lr, sr: int, n_fft: int, hop: int, music_dbfs: float)
     return freqs, med.cpu().numpy(), used
 
 
+def stable_classes(codes, margin=2):
+    """find_stable_frames' rule on int8 codes: 1 / 2 where the +-margin window is
+    all C1 / all C2, else 0."""
+    codes = np.asarray(codes, np.int8)
+    n = len(codes)
+    cls = np.zeros(n, np.int8)
+    if n - 2 * margin <= 0:
+        return cls
+    win = np.lib.stride_tricks.sliding_window_view(codes, 2 * margin + 1)
+    cls[margin:n - margin][np.all(win == 1, axis=1)] = 1
+    cls[margin:n - margin][np.all(win == 2, axis=1)] = 2
+    return cls
+
+
 def _stable_classes(states, margin=2):
     """int8 per state index: 1 = stable C1, 2 = stable C2, 0 = neither
     (validate_layer1.find_stable_frames' rule, vectorised)."""
@@ -196,14 +214,7 @@ def _stable_classes(states, margin=2):
         s = None
     if s is None:
         s = np.asarray([1 if v == "C1" else (2 if v == "C2" else 0) for v in states], np.int8)
-    n = len(s)
-    cls = np.zeros(n, np.int8)
-    if n - 2 * margin <= 0:
-        return cls
-    win = np.lib.stride_tricks.sliding_window_view(s, 2 * margin + 1)  # starts at i - margin
-    cls[margin:n - margin][np.all(win == 1, axis=1)] = 1
-    cls[margin:n - margin][np.all(win == 2, axis=1)] = 2
-    return cls
+    return stable_classes(s, margin)
 
 
 def find_stable_frames(states, margin=2):
@@ -253,3 +264,173 @@ def compute_conditional_spectrum(x, y, sr, states, n_fft, hop, level_threshold=-
         else:
             out.append(np.zeros(nb))
     return freqs, out[0], out[1], sel[0][1], sel[1][1]
+
+
+# ---------------------------------------------------------------------------
+# acceptance validators (SURVEY.md §8 row f9): the device pieces shared by
+# validate_layer1.py and verify_tomatis_15db_v2.py
+# ---------------------------------------------------------------------------
+
+def band_bins(freqs, f_lo, f_hi):
+    """[b0, b1): the bins with f_lo <= freqs <= f_hi (both ends included, as the
+    validators' masks); (0, 0) when there is none."""
+    idx = np.nonzero((freqs >= f_lo) & (freqs <= f_hi))[0]
+    return (int(idx[0]), int(idx[-1]) + 1) if len(idx) else (0, 0)
+
+
+def pair_on_device(x, y, max_short):
+    """x and y as resident [n, ch] tensors of one length: y is cut to len(x), or
+    zero-extended when it is shorter by at most ``max_short`` frames (what the
+    validators' n_fft // 2 of zero padding does to a frame that runs past y)."""
+    torch = _torch()
+    xd = _dev(x, ch=True)
+    yd = _dev(y, ch=True)
+    n, ch = xd.shape
+    if ch not in (1, 2) or yd.shape[1] != ch:
+        raise ValueError("x and y must have the same channel count (1 or 2)")
+    if yd.shape[0] < n:
+        if n - yd.shape[0] > max_short:
+            raise ValueError(f"y is {n - yd.shape[0]} frames shorter than x (at most {max_short})")
+        yd = torch.cat([yd, torch.zeros((n - yd.shape[0], ch), dtype=torch.float32,
+                                        device="cuda")])
+    return xd, yd[:n].contiguous()
+
+
+def padded_frame_levels(xd, n_fft, hop):
+    """The validators' level grid (validate_layer1.py:116-161,
+    verify_tomatis_15db_v2.py:107-123): x zero-padded by n_fft // 2 on both sides
+    on the device, frames at k * hop of the padded signal while they fit, kept
+    where 0 <= k * hop - n_fft // 2 < n  ->  (levels float64, padded starts int64).
+    r comes from tomatis_an_frame_r (bit-exact); the level is the reference's own
+    numpy expression on the host (dsp.r_to_level)."""
+    torch = _torch()
+    n, ch = xd.shape
+    pad = n_fft // 2
+    if n == 0:
+        return np.zeros(0), np.zeros(0, np.int64)
+    xp = torch.zeros((n + 2 * pad, ch), dtype=torch.float32, device="cuda")
+    xp[pad:pad + n] = xd
+    r = _frame_r(xp, n + 2 * pad, ch, n_fft, hop, AN_LEVEL_CHMEAN).cpu().numpy()
+    s = np.arange(len(r), dtype=np.int64) * hop
+    keep = (s - pad >= 0) & (s - pad < n)
+    return dsp.r_to_level(r[keep]), s[keep]
+
+
+def state_codes(states):
+    """int8 1 / 2 per state from a list of 'C1' / 'C2' (or an integer array)."""
+    if isinstance(states, np.ndarray) and states.dtype.kind in "iu":
+        return states.astype(np.int8)
+    if len(states) == 0:
+        return np.zeros(0, np.int8)
+    b = np.frombuffer("".join(states).encode("ascii"), np.uint8)
+    if b.size != 2 * len(states):
+        raise ValueError("states must be 'C1' / 'C2'")
+    return np.where(b[1::2] == ord("2"), 2, 1).astype(np.int8)
+
+
+def state_names(codes):
+    return np.where(np.asarray(codes) == 2, "C2", "C1").tolist()
+
+
+def _f32_at_least(v):
+    f = np.float32(v)
+    return f if float(f) >= v else np.nextafter(f, np.float32(np.inf))
+
+
+def _f32_at_most(v):
+    f = np.float32(v)
+    return f if float(f) <= v else np.nextafter(f, np.float32(-np.inf))
+
+
+class GateScan:
+    """The validators' gate automaton (validate_layer1.py:141-157,
+    verify_tomatis_15db_v2.py:126-152) over resident levels: one
+    tomatis_cal_gate_grid launch per threshold pair.  The levels are float32
+    values held in float64, which the reference compares with float64 thresholds;
+    the kernel gets the smallest float32 >= Ton and the largest <= Toff, so every
+    comparison comes out as the reference's."""
+
+    def __init__(self, levels, starts):
+        torch = _torch()
+        lv64 = np.asarray(levels, np.float64)
+        lv32 = lv64.astype(np.float32)
+        if not np.array_equal(lv32.astype(np.float64), lv64, equal_nan=True):
+            raise ValueError("gate levels must be float32 values (20 log10(r + EPS) of a float32 r)")
+        self.n = len(lv32)
+        self.lv = torch.from_numpy(lv32).cuda()
+        self.st = torch.from_numpy(np.ascontiguousarray(starts, np.int64)).cuda()
+        self.tg = torch.ones(max(1, self.n), dtype=torch.int32, device="cuda")  # all C1
+        self.out = torch.empty(2, dtype=torch.int32, device="cuda")
+        self.states = None
+
+    def run(self, Ton, Toff, up_delay, want_states=False):
+        """-> (C2 count, switch count[, int8 states])."""
+        from ._lib import GATE_CAND_DTYPE
+        torch = _torch()
+        if self.n == 0:
+            return (0, 0, np.zeros(0, np.int8)) if want_states else (0, 0)
+        c = np.zeros(1, GATE_CAND_DTYPE)
+        c["t_on"], c["t_off"] = _f32_at_least(float(Ton)), _f32_at_most(float(Toff))
+        c["up_delay"] = int(up_delay)
+        cb = torch.from_numpy(c.view(np.uint8)).cuda()
+        if want_states and self.states is None:
+            self.states = torch.empty(self.n, dtype=torch.uint8, device="cuda")
+        check(lib().tomatis_cal_gate_grid(ptr(self.lv), self.n, ptr(self.st), ptr(self.tg),
+                                          ptr(cb), 1, ptr(self.out),
+                                          ptr(self.states if want_states else None),
+                                          stream_handle()), "cal_gate_grid")
+        c2, sw = (int(v) for v in self.out.cpu().numpy())
+        if want_states:
+            return c2, sw, self.states.cpu().numpy().astype(np.int8)
+        return c2, sw
+
+
+def verify_spectra(xd, yd, n_fft, hop, anchor=None, bands=None, fused=True, win=None):
+    """The validator's per-frame spectra of a resident pair (tm_analysis.hip
+    k_an_verify): the anchored ratio rows [F, n_fft/2+1] for ``anchor`` = (a0, a1)
+    and / or the band energies [F, 4] for ``bands`` = (lo0, lo1, hi0, hi1).  With
+    both, one launch forms them from one transform (``fused``), or two launches
+    do; the bits are the same.  ``win``: the resident float32 Hann window, where the
+    caller keeps one (default: built and uploaded here)."""
+    _check_n_fft(n_fft)
+    torch = _torch()
+    n, ch = xd.shape
+    F = max(0, _n_frames(n, n_fft, hop))
+    nb = n_fft // 2 + 1
+    if win is None:
+        win = torch.from_numpy(dsp.hann(n_fft)).cuda()
+    rows = torch.empty((F, nb), dtype=torch.float32, device="cuda") if anchor is not None else None
+    be = torch.empty((F, 4), dtype=torch.float32, device="cuda") if bands is not None else None
+    if F == 0:
+        return rows, be
+    L, hs = lib(), stream_handle()
+    if rows is not None and be is not None and fused:
+        check(L.tomatis_an_verify_pair(ptr(xd), ptr(yd), n, ch, n_fft, hop, *anchor, *bands,
+                                       ptr(win), ptr(rows), ptr(be), hs), "an_verify_pair")
+        return rows, be
+    if rows is not None:
+        check(L.tomatis_an_anchored_ratio(ptr(xd), ptr(yd), n, ch, n_fft, hop, *anchor, ptr(win),
+                                          ptr(rows), hs), "an_anchored_ratio")
+    if be is not None:
+        check(L.tomatis_an_pair_band_energy(ptr(xd), ptr(yd), n, ch, n_fft, hop, *bands, ptr(win),
+                                            ptr(be), hs), "an_pair_band_energy")
+    return rows, be
+
+
+def sum_f64(t):
+    """Float64 sum of a resident float32 tensor (tomatis_sum_f64: fixed order)."""
+    from ._lib import SUM_DOUBLES
+    torch = _torch()
+    t = t.reshape(-1)
+    out = torch.empty(SUM_DOUBLES, dtype=torch.float64, device="cuda")
+    check(lib().tomatis_sum_f64(ptr(t), t.numel(), ptr(out), stream_handle()), "sum_f64")
+    return float(out[0].item())
+
+
+def absmax(t):
+    """np.max(np.abs(t)) of a resident float32 tensor as np.float32 (tomatis_absmax)."""
+    torch = _torch()
+    t = t.reshape(-1)
+    bits = torch.zeros(1, dtype=torch.int32, device="cuda")
+    check(lib().tomatis_absmax(ptr(t), t.numel(), ptr(bits), stream_handle()), "absmax")
+    return np.array([bits.item()], np.int32).view(np.float32)[0]

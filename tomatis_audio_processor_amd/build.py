@@ -10,7 +10,8 @@ Nine translation units, compiled in parallel and linked into one C-ABI library:
   ``TOMATIS_TRANSFORM_SCHED`` selects another LLVM machine scheduler for
   experiments — measured within 1 % of the default);
 * ``tm_analysis.hip``  analysis spectra for the validators / calibration tools
-  (SURVEY.md §8 rows f3/f4), the fused mean log-power spectrum of row f8;
+  (SURVEY.md §8 rows f3/f4), the fused mean log-power spectrum of row f8, the
+  acceptance validators' anchored ratio rows, band energies and float64 sum (row f9);
 * ``tm_flacenc.hip``   FLAC frames encoded on the device (row f1's egress);
 * ``tm_flacdec.hip``   FLAC frames decoded on the device (row f1's ingest);
 * ``tm_declick.hip``   the de-click stage: MAD click detector and linear

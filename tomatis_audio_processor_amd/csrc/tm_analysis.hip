@@ -16,6 +16,10 @@
 //   compare_to_baseline.avg_spectrum_db        src/compare_to_baseline.py:105-122
 //       mean over frames, in float64, of 10 log10(|rfft(win * power_mono)|^2 + EPS)
 //                                              -> k_an_spec_mean, k_an_spec_mean_fold
+//   verify_tomatis_15db_v2 (the acceptance validator)  src/verify_tomatis_15db_v2.py
+//       :307-354 ratio rows divided by their mean over an anchor band, :451-470
+//       band energies of input and output, :90 the DC mean
+//                                              -> k_an_verify, k_an_sum_part / _fold
 //
 // Frames: f = 0 .. F-1 start at f*hop, F = 1 + (n - n_fft) / hop (every frame
 // lies inside the signal, as in all three reference loops).
@@ -678,6 +682,161 @@ __global__ __launch_bounds__(kT) void k_an_spec_ratio(SpecArgs A) {
   }
 }
 
+// Acceptance validator v2 (verify_tomatis_15db_v2.py): the per-frame work of its
+// sections C and D on an input/output pair, one workgroup per frame and one
+// transform of x_c + i y_c per channel, as k_an_spec_ratio.
+//   ROWS  (:307-354)  ratio[k] = mean_c|Y_c| / max(mean_c|X_c|, 1e-10) exactly as
+//     k_an_spec_ratio forms it, then g = mean(ratio[a0:a1]) and the row stored as
+//     ratio / g when the anchor range is not empty and g > 0, else as it is (the
+//     reference's np.mean of an empty slice is NaN, and NaN > 0 is false).
+//   BANDS (:451-470)  P_x[k] = mean_c |X_c[k]|^2 (re^2 + im^2 in float32), P_y
+//     likewise; bands[f] = (sum P_x[lo), sum P_x[hi), sum P_y[lo), sum P_y[hi)),
+//     the two ranges independent and possibly empty as in k_an_band_pair.
+// The row stays in registers after the split (bins t, t + kT, ...); the anchor
+// sum and the four band sums go through one fixed-order block reduction (a
+// thread's bins ascending, a shuffle tree, the four waves in order): no atomics,
+// the same bits in every run, and the same bits whether a launch forms the rows,
+// the bands or both.
+struct VerArgs {
+  SpecArgs S;    // out = rows [F][n_bins] (ROWS), band = lo0, lo1, hi0, hi1 (BANDS)
+  float* bands;  // [F][4]
+  int a0, a1;    // anchor bins [a0, a1)
+};
+
+template <int CH, int M, bool BLUE, bool ROWS, bool BANDS>
+__global__ __launch_bounds__(kT) void k_an_verify(VerArgs V) {
+  __shared__ float2 buf[M];
+  __shared__ float red[kT / 64][5];
+  const SpecArgs& A = V.S;
+  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
+  constexpr int kUR = ROWS ? kMaxUB : 1, kUP = BANDS ? kMaxUB : 1;
+  const int f = blockIdx.x;
+  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
+  const int64_t p0 = (int64_t)f * A.hop;
+  float ax[kUR], ay[kUR], px[kUP], py[kUP];
+#pragma unroll
+  for (int u = 0; u < kUR; ++u) ax[u] = ay[u] = 0.f;
+#pragma unroll
+  for (int u = 0; u < kUP; ++u) px[u] = py[u] = 0.f;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    for (int i = threadIdx.x; i < n; i += kT) {
+      const float w = A.win[i];
+      const int64_t q = (p0 + i) * CH + c;
+      buf[i] = make_float2(A.x[q] * w, A.y[q] * w);
+    }
+    __syncthreads();
+    lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
+#pragma unroll
+    for (int u = 0; u < kMaxUB; ++u) {
+      const int k = threadIdx.x + u * kT;
+      if (k < A.n_bins) {
+        const float2 zk = buf[k], zm = buf[mirror(k, n)];
+        const float xr = 0.5f * (zk.x + zm.x), xi = 0.5f * (zk.y - zm.y);
+        const float yr = 0.5f * (zk.y + zm.y), yi = -0.5f * (zk.x - zm.x);
+        if constexpr (ROWS) {
+          ax[u] = ax[u] + hypotf(xr, xi);  // X += |rfft(x_c * win)|
+          ay[u] = ay[u] + hypotf(yr, yi);
+        }
+        if constexpr (BANDS) {
+          px[u] = px[u] + (xr * xr + xi * xi);  // X += |rfft(x_c * win)|**2
+          py[u] = py[u] + (yr * yr + yi * yi);
+        }
+      }
+    }
+    __syncthreads();  // buf reused by the next channel
+  }
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // anchor, (x, lo), (x, hi), (y, lo), (y, hi)
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) {
+    const int k = threadIdx.x + u * kT;
+    if (k < A.n_bins) {
+      if constexpr (ROWS) {
+        float X = (CH == 1) ? ax[u] : ax[u] * 0.5f;  // X /= ch
+        const float Y = (CH == 1) ? ay[u] : ay[u] * 0.5f;
+        X = fmaxf(X, 1e-10f);                        // np.maximum(X, 1e-10)
+        ax[u] = Y / X;
+        if (k >= V.a0 && k < V.a1) acc[0] = acc[0] + ax[u];
+      }
+      if constexpr (BANDS) {
+        const float PX = (CH == 1) ? px[u] : px[u] * 0.5f;
+        const float PY = (CH == 1) ? py[u] : py[u] * 0.5f;
+        if (k >= A.band[0] && k < A.band[1]) {
+          acc[1] = acc[1] + PX;
+          acc[3] = acc[3] + PY;
+        }
+        if (k >= A.band[2] && k < A.band[3]) {
+          acc[2] = acc[2] + PX;
+          acc[4] = acc[4] + PY;
+        }
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    float v = acc[j];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[w][j] = v;
+  }
+  __syncthreads();
+  if constexpr (BANDS) {
+    if (threadIdx.x < 4) {
+      const int j = 1 + threadIdx.x;
+      float v = 0.f;
+      for (int i = 0; i < kT / 64; ++i) v += red[i][j];
+      V.bands[(int64_t)f * 4 + threadIdx.x] = v;
+    }
+  }
+  if constexpr (ROWS) {
+    float s = 0.f;
+    for (int i = 0; i < kT / 64; ++i) s += red[i][0];
+    const int na = V.a1 - V.a0;
+    const float g = na > 0 ? s / (float)na : 0.f;
+    const bool scale = na > 0 && g > 0.f;  // anchor_gain > 0 (NaN: false)
+    float* o = A.out + (int64_t)f * A.n_bins;
+#pragma unroll
+    for (int u = 0; u < kMaxUB; ++u) {
+      const int k = threadIdx.x + u * kT;
+      if (k < A.n_bins) o[k] = scale ? ax[u] / g : ax[u];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// float64 sum of a float32 buffer (np.mean(y) of check_engineering,
+// verify_tomatis_15db_v2.py:90): kSumGroups partial sums over a fixed grid (a
+// constant of the source, not of the device), element i in group (i / kT) mod
+// kSumGroups, each folded by a shuffle tree and the four waves in order; then the
+// partial sums in index order.  The same bits in every run.
+// ---------------------------------------------------------------------------
+constexpr int kSumGroups = 1024;
+
+__global__ __launch_bounds__(kT) void k_an_sum_part(const float* __restrict__ x, int64_t n,
+                                                    double* __restrict__ part) {
+  __shared__ double sm[kT / 64];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < n; i += (int64_t)kSumGroups * kT)
+    s += (double)x[i];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < kT / 64; ++i) t += sm[i];
+    part[blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_an_sum_fold(const double* __restrict__ part,
+                                                     double* __restrict__ out) {
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < kSumGroups; ++i) s += part[i];
+    out[0] = s;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // reductions over frames
 // ---------------------------------------------------------------------------
@@ -1000,6 +1159,86 @@ int tomatis_an_band_energy(const float* x, int64_t n, int32_t n_fft, int32_t hop
     hipLaunchKernelGGL((k_an_band_pair<decltype(m)::value, decltype(b)::value>), g, dim3(kT), 0,
                        s, A);
   });
+}
+
+}  // extern "C"
+
+namespace {
+
+// rows and / or bands of an input/output pair in one launch of k_an_verify
+int an_verify(const float* x, const float* y, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
+              int32_t a0, int32_t a1, int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1,
+              const float* win, float* rows, float* bands, void* hs) {
+  if (!x || !y || !win || (!rows && !bands) || hop < 1 || ch < 1 || n_fft < 1 || n < 0)
+    return TOMATIS_E_ARG;
+  if (ch != 1 && ch != 2) return TOMATIS_E_UNSUPPORTED;
+  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
+  const int nb = n_fft / 2 + 1;
+  if (a0 < 0 || a1 < a0 || a1 > nb) return TOMATIS_E_ARG;
+  if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
+  if (n < n_fft) return TOMATIS_OK;
+  const int64_t F = 1 + (n - n_fft) / hop;
+  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hs;
+  VerArgs V{{x, y, win, nullptr, nullptr, nullptr, rows, n_fft, 0, hop, (int)F, nb, 1.0f,
+             {lo0, lo1, hi0, hi1}},
+            bands, a0, a1};
+  int rc = dft_args(n_fft, s, &V.S);
+  if (rc != TOMATIS_OK) return rc;
+  const dim3 g((unsigned)F);
+  const int mode = (rows ? 1 : 0) | (bands ? 2 : 0);
+  return dispatch_m(V.S, [&](auto m, auto b) {
+    constexpr int MM = decltype(m)::value;
+    constexpr bool BL = decltype(b)::value;
+#define TM_AN_VERIFY(CHN, R, B) \
+  hipLaunchKernelGGL((k_an_verify<CHN, MM, BL, R, B>), g, dim3(kT), 0, s, V)
+    if (ch == 1) {
+      if (mode == 1) TM_AN_VERIFY(1, true, false);
+      else if (mode == 2) TM_AN_VERIFY(1, false, true);
+      else TM_AN_VERIFY(1, true, true);
+    } else {
+      if (mode == 1) TM_AN_VERIFY(2, true, false);
+      else if (mode == 2) TM_AN_VERIFY(2, false, true);
+      else TM_AN_VERIFY(2, true, true);
+    }
+#undef TM_AN_VERIFY
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int tomatis_an_anchored_ratio(const float* x, const float* y, int64_t n, int32_t ch,
+                              int32_t n_fft, int32_t hop, int32_t a0, int32_t a1,
+                              const float* win, float* rows, void* hs) {
+  if (!rows) return TOMATIS_E_ARG;
+  return an_verify(x, y, n, ch, n_fft, hop, a0, a1, 0, 0, 0, 0, win, rows, nullptr, hs);
+}
+
+int tomatis_an_pair_band_energy(const float* x, const float* y, int64_t n, int32_t ch,
+                                int32_t n_fft, int32_t hop, int32_t lo0, int32_t lo1,
+                                int32_t hi0, int32_t hi1, const float* win, float* bands,
+                                void* hs) {
+  if (!bands) return TOMATIS_E_ARG;
+  return an_verify(x, y, n, ch, n_fft, hop, 0, 0, lo0, lo1, hi0, hi1, win, nullptr, bands, hs);
+}
+
+int tomatis_an_verify_pair(const float* x, const float* y, int64_t n, int32_t ch, int32_t n_fft,
+                           int32_t hop, int32_t a0, int32_t a1, int32_t lo0, int32_t lo1,
+                           int32_t hi0, int32_t hi1, const float* win, float* rows, float* bands,
+                           void* hs) {
+  if (!rows || !bands) return TOMATIS_E_ARG;
+  return an_verify(x, y, n, ch, n_fft, hop, a0, a1, lo0, lo1, hi0, hi1, win, rows, bands, hs);
+}
+
+int tomatis_sum_f64(const float* x, int64_t n, double* out, void* hs) {
+  if (!x || !out || n < 0) return TOMATIS_E_ARG;
+  hipStream_t s = (hipStream_t)hs;
+  double* part = out + 1;
+  hipLaunchKernelGGL(k_an_sum_part, dim3(kSumGroups), dim3(kT), 0, s, x, n, part);
+  hipLaunchKernelGGL(k_an_sum_fold, dim3(1), dim3(64), 0, s, (const double*)part, out);
+  return an_launch();
 }
 
 int64_t tomatis_an_spectrum_mean_work_doubles(int64_t n_frames, int32_t n_bins) {
