@@ -45,6 +45,10 @@
  *   src/calibrate_to_baseline_v2.py:84-109,      tomatis_cal_gate_grid
  *       231-265 (simulate_state x the gain /
  *       up-delay / hysteresis / T search grid)
+ *   src/find_main_segment.py:5-10,66-72          tomatis_an_frame_power_mean
+ *       (win_rms_dbfs over the hop grid)
+ *   src/cut_tomatis_d.py:32-33 with the           tomatis_resample_poly
+ *       workflow's -ss / -t / -ar 48000
  *
  * Conventions: every call is asynchronous on the given hipStream_t and returns
  * an int status (0 = ok, <0 = error, see TOMATIS_E_*); no exceptions cross the
@@ -510,6 +514,16 @@ int tomatis_synth_fill(float* x, int64_t n, int32_t ch, int32_t sr, uint32_t see
 int tomatis_an_frame_r(const float* x, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
                        int32_t level_mode, float scale, float* r_out, void* hip_stream);
 
+/* Per-frame mean power of find_main_segment's win_rms_dbfs
+ * (src/find_main_segment.py:8-9): x interleaved stereo, out[f] = np.mean(p) of
+ * p[i] = (l l + r r) * 0.5 over the window of `win` frames at f * hop, every
+ * product and sum rounded to float32, summed in numpy's pairwise order and
+ * divided by float32(win): bit-exact.  The sqrt / log10 of :9-10 stay with
+ * numpy on the host.  1 <= win <= 65536 (above: TOMATIS_E_UNSUPPORTED),
+ * hop >= 1; F = 1 + (n - win) / hop frames for n >= win, else none.  out: F floats. */
+int tomatis_an_frame_power_mean(const float* x, int64_t n, int32_t win, int32_t hop, float* out,
+                                void* hip_stream);
+
 /* mask[f] = level predicate on r bits (dsp.gate_bits form) && (cls == NULL ||
  * cls[f] == cls_want); keep_above = 1: level >= T <=> (b >= thr) xor b in exc;
  * keep_above = 0: level > T <=> !((b <= thr) xor b in exc).  exc_host: up to 4
@@ -826,6 +840,29 @@ int tomatis_an_verify_pair(const float* x, const float* y, int64_t n, int32_t ch
  * grid (element i in group (i / 256) mod 1024), folded in index order; the same
  * bits in every run and on every device.  n == 0: 0. */
 int tomatis_sum_f64(const float* x, int64_t n, double* out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
+ * Audio resampler (workflow step 2.1; tm_resample.hip):
+ * scipy.signal.resample_poly(x[start:start + len], up, down, axis=0), the call
+ * behind every rate change of the reference (src/layer2_analyze_eq.py:31,43,
+ * src/compare_audio.py:33-34, src/calibrate_to_baseline_v2.py:60,72) applied to
+ * the PCM itself, which the workflow does with `ffmpeg -ss .. -t .. -ar 48000`.
+ * x: float32 [n_total][channels] interleaved, out: [ceil(len up / down)][channels].
+ * With half = (n_taps - 1) / 2,
+ *   out[j][c] = sum_i taps[down j + half - up i] x[start + i][c],  0 <= i < len,
+ * the tap index inside [0, n_taps): frames outside [start, start + len) count as
+ * zero even where they are live in x (a cut and a resample in one pass).  taps =
+ * float32(firwin(20 M + 1, 1 / M, ("kaiser", 5.0))) * float32(up), M = max(up,
+ * down), is scipy's own filter for float32 input.  Float32 FMA chains in an order
+ * fixed by (up, down, n_taps) and the output's phase: an output's bits depend on
+ * its taps and its ceil(n_taps / up) input samples only.
+ * TOMATIS_E_ARG: a null pointer, a bad range (len < 1 included), an even n_taps,
+ * up == down, gcd(up, down) != 1, channels outside 1..8; TOMATIS_E_UNSUPPORTED:
+ * max(up, down) > 512, down > 8 up, n_taps > 20 max(up, down) + 1, n_total above
+ * 2^48; both before anything is read. */
+int tomatis_resample_poly(const float* x, int64_t n_total, int64_t start, int64_t len,
+                          int32_t channels, int32_t up, int32_t down, const float* taps,
+                          int32_t n_taps, float* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,10 @@ _SIGS = {
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, _P, _P, _P, _P]),
     "tomatis_sum_f64": (C.c_int, [_P, C.c_int64, _P, _P]),
+    # main-segment finder, cut and resampler
+    "tomatis_an_frame_power_mean": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    "tomatis_resample_poly": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                        C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

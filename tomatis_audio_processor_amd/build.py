@@ -1,6 +1,6 @@
 """Build ``libtomatis_hip.so`` in-tree with hipcc for gfx950 (no cmake/ninja needed).
 
-Nine translation units, compiled in parallel and linked into one C-ABI library:
+Ten translation units, compiled in parallel and linked into one C-ABI library:
 
 * ``tm_kernels.hip``   levels, gate, limiter and the ``extern "C"`` launches;
 * ``tm_plan.cpp``      the plan: stream validation, path selection, every work
@@ -20,7 +20,9 @@ Nine translation units, compiled in parallel and linked into one C-ABI library:
   direct cross-correlation, arg-max (row f6), the residual means of row f7, the
   time-domain sums of row f8;
 * ``tm_fftcorr.hip``   the power-of-two FFT in global memory and the "full"
-  correlation built on it (row f7).
+  correlation built on it (row f7);
+* ``tm_resample.hip``  the polyphase audio resampler of workflow step 2.1
+  (row f10): ``resample_poly`` for interleaved multichannel PCM.
 """
 from __future__ import annotations
 
@@ -47,6 +49,7 @@ UNITS = {  # source -> extra flags
     "tm_declick.hip": [],
     "tm_align.hip": [],
     "tm_fftcorr.hip": [],
+    "tm_resample.hip": [],
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
                                         "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h",

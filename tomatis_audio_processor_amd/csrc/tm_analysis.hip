@@ -68,7 +68,9 @@ constexpr int kT = 256;                // threads per spectrum workgroup
 constexpr int kMaxTreeN = 8192;        // k_an_frame_r: powers of two in [256, 8192]
 constexpr int kMaxM = 16384;           // largest FFT in LDS (128 KiB of float2)
 constexpr int kMinN = 16;              // smallest spectrum n_fft
-constexpr int kPwMax = 256;            // k_an_frame_r_pw leaves (n_fft <= 16384)
+constexpr int kPwMax = 512;            // k_an_frame_r_pw leaves (windows <= 65536)
+constexpr int kLevelPowerMean = 2;     // k_an_frame_r_pw only: tomatis_an_frame_power_mean's term
+constexpr int kMaxMeanWin = 65536;     // tomatis_an_frame_power_mean
 constexpr float kEps = 1e-12f;
 
 int an_fail(hipError_t e) { return e == hipSuccess ? TOMATIS_OK : TOMATIS_E_HIP; }
@@ -269,11 +271,16 @@ __device__ __forceinline__ float m2_at(const float* __restrict__ x, int64_t p, f
   if constexpr (MODE == TOMATIS_AN_LEVEL_POWER_MONO) {
     const float m = power_mono(x, p, sc);
     return m * m;
+  } else if constexpr (MODE == kLevelPowerMean) {
+    // find_main_segment.py:8: (l l + r r) * 0.5, every operation rounded (sc unused)
+    const float l = x[2 * p], r = x[2 * p + 1];
+    return __fmul_rn(__fadd_rn(__fmul_rn(l, l), __fmul_rn(r, r)), 0.5f);
   } else {
     return m2_chmean<CH>(x, p, sc);
   }
 }
 
+// MODE kLevelPowerMean writes the mean itself (np.mean(p), :9), the others r
 template <int MODE, int CH>
 __global__ __launch_bounds__(256) void k_an_frame_r_pw(const float* __restrict__ x, int n_fft,
                                                        int hop, float sc,
@@ -318,7 +325,8 @@ __global__ __launch_bounds__(256) void k_an_frame_r_pw(const float* __restrict__
         stk[sp - 1] = stk[sp - 1] + b;
       }
     }
-    r_out[f] = sqrtf(stk[0] / (float)n_fft + kEps);
+    if constexpr (MODE == kLevelPowerMean) r_out[f] = __fdiv_rn(stk[0], (float)n_fft);
+    else r_out[f] = sqrtf(stk[0] / (float)n_fft + kEps);
   }
 }
 
@@ -1069,6 +1077,21 @@ int tomatis_an_frame_r(const float* x, int64_t n, int32_t ch, int32_t n_fft, int
   else
     hipLaunchKernelGGL((k_an_frame_r_pw<TOMATIS_AN_LEVEL_CHMEAN, 2>), g, dim3(256), 0, s, x,
                        n_fft, hop, scale, q.leaf, q.n_leaf, q.prog, q.n_prog, r_out);
+  return an_launch();
+}
+
+int tomatis_an_frame_power_mean(const float* x, int64_t n, int32_t win, int32_t hop, float* out,
+                                void* hs) {
+  if (!x || !out || n < 0 || win < 1 || hop < 1) return TOMATIS_E_ARG;
+  if (win > kMaxMeanWin) return TOMATIS_E_UNSUPPORTED;
+  if (n < win) return TOMATIS_OK;
+  const int64_t F = 1 + (n - win) / hop;
+  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  PwProg q;
+  const int rc = pw_program(win, &q);
+  if (rc != TOMATIS_OK) return rc;
+  hipLaunchKernelGGL((k_an_frame_r_pw<kLevelPowerMean, 2>), dim3((unsigned)F), dim3(256), 0,
+                     (hipStream_t)hs, x, win, hop, 1.0f, q.leaf, q.n_leaf, q.prog, q.n_prog, out);
   return an_launch();
 }
 
