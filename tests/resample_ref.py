@@ -6,7 +6,7 @@ from __future__ import annotations
 import functools
 
 import numpy as np
-from scipy.signal import firwin
+from scipy.signal import firwin, resample_poly
 
 from tests.rational_ref import resample_direct as _direct_1d
 from tests.stft_ref import white as _white
@@ -34,6 +34,27 @@ def resample_direct(x, up, down, h, dtype=np.float64):
     if x.ndim == 1:
         return _direct_1d(x, up, down, h, dtype)
     return np.stack([_direct_1d(x[:, c], up, down, h, dtype) for c in range(x.shape[1])], axis=1)
+
+
+def resample_scipy64(x, up, down):
+    """scipy's float64 ``resample_poly`` with the float32 design as its window: the
+    statement at the lengths where ``resample_direct``'s term matrix is too large
+    (tests/test_resample_ref.py holds the two together to 1e-12 of the peak).
+    scipy scales the window by up in float64, ``taps`` in float32: the same taps
+    where up is a power of two, which holds wherever the tests use this."""
+    return resample_poly(np.asarray(x, np.float64), up, down, axis=0, window=taps_unscaled(up, down))
+
+
+def random_taps(seed, n_taps):
+    """A filter with no symmetry: float32 draws of a standard normal."""
+    return np.random.default_rng(seed).standard_normal(n_taps).astype(np.float32)
+
+
+def tapless(n_out, up, down, n_taps):
+    """Mask of the output frames whose phase (down j + half) mod up has no tap
+    (n_taps < up): they are +0 whatever the input is."""
+    half = (n_taps - 1) // 2
+    return (down * np.arange(n_out, dtype=np.int64) + half) % up >= n_taps
 
 
 @functools.lru_cache(maxsize=None)

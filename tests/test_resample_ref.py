@@ -9,6 +9,7 @@ from tests import resample_ref as rs
 
 RATIOS = [(160, 147), (80, 147), (1, 2), (3, 2), (2, 1), (320, 147), (1, 4)]
 ALL_RATIOS = RATIOS + [(40, 147), (6, 1), (3, 1), (512, 511), (1, 8)]
+ALL_RATIOS += [(4, 7), (2, 3)]   # K = 36 and K = 31: K mod 4 of 0 and 3
 
 
 @pytest.mark.parametrize("ch", [1, 2])
@@ -22,6 +23,30 @@ def test_statement_is_resample_poly(up, down, n, ch):
     assert got.shape == want.shape == (-(-n * up // down), ch)
     peak = float(np.max(np.abs(want)))
     assert float(np.max(np.abs(got - want))) <= 1e-12 * peak
+
+
+@pytest.mark.parametrize("n", [1, 23, 1000])
+@pytest.mark.parametrize("up,down", [(512, 511), (1, 8), (4, 7), (2, 3)])
+def test_scipy64_is_the_statement(up, down, n):
+    """``rs.resample_scipy64``, which stands in for the statement at the long
+    lengths of tests/test_gpu_resample_paths.py, is the statement."""
+    x = rs.white(4300 + up + down, 1000, 8)[:n]
+    want = rs.resample_scipy64(x, up, down)
+    got = rs.resample_direct(x, up, down, rs.taps(up, down), np.float64)
+    assert got.shape == want.shape == (-(-n * up // down), 8)
+    peak = float(np.max(np.abs(want)))
+    assert peak > 0.0
+    assert float(np.max(np.abs(got - want))) <= 1e-12 * peak
+
+
+def test_tapless_phases():
+    h = rs.random_taps(1, 3)
+    x = rs.white(4400, 50, 1)[:, 0]
+    y = rs.resample_direct(x, 5, 3, h, np.float64)
+    mask = rs.tapless(len(y), 5, 3, 3)
+    assert mask.any() and not mask.all()
+    assert not np.any(y[mask]) and np.all(y[~mask][1:-1] != 0.0)
+    assert not rs.tapless(40, 2, 3, 15).any()
 
 
 @pytest.mark.parametrize("up,down", ALL_RATIOS)

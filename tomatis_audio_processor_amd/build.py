@@ -22,7 +22,9 @@ Ten translation units, compiled in parallel and linked into one C-ABI library:
 * ``tm_fftcorr.hip``   the power-of-two FFT in global memory and the "full"
   correlation built on it (row f7);
 * ``tm_resample.hip``  the polyphase audio resampler of workflow step 2.1
-  (row f10): ``resample_poly`` for interleaved multichannel PCM.
+  (row f10): ``resample_poly`` for interleaved multichannel PCM; its index
+  arithmetic is ``tm_resample_plan.h``, host and device, which
+  ``tools/resample_plan_check.cpp`` checks on the CPU.
 """
 from __future__ import annotations
 
@@ -53,7 +55,7 @@ UNITS = {  # source -> extra flags
 }
 DEPS = [os.path.join(CSRC, f) for f in (*UNITS, "tm_common.h", "tm_fft.h", "tm_shared.h",
                                         "tm_lds_fft.h", "tm_host_dsp.h", "tm_gate.h",
-                                        "tm_layout.h", "tm_plan.h")] + \
+                                        "tm_layout.h", "tm_plan.h", "tm_resample_plan.h")] + \
        [os.path.join(ROOT, "include", "tomatis_hip.h"), os.path.abspath(__file__)]
 OUT = os.path.join(HERE, "libtomatis_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

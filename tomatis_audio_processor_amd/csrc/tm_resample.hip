@@ -37,26 +37,19 @@
 //    not depend on start, len, the tile, the channel count or the run.
 // T is the largest power of two <= 1024 whose stage and table fit 64 KiB; it
 // depends on (up, down, n_taps, channels) alone (resample.outputs_per_workgroup).
+//
+// Every index below (the plan, the argument rule, what a tile and an element
+// compute, the table's source) is a function of tm_resample_plan.h, host and
+// device, which tools/resample_plan_check.cpp checks on the CPU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/tomatis_hip.h"
+#include "tm_resample_plan.h"
 
 namespace {
 
-typedef long long i64;
-
-constexpr int kT = 256;             // threads per workgroup
-constexpr int kMaxTile = 1024;      // output frames per workgroup, at most
-constexpr int kLdsBytes = 64 * 1024;
-constexpr int kMaxRatio = 512;      // max(up, down)
-constexpr int kMaxDecim = 8;        // down <= kMaxDecim up
-constexpr int kMaxCh = 8;
-constexpr int kInFlight = 4;        // 16-byte loads in flight per thread while staging
-
-struct RsPlan {
-  int up, down, n_taps, ch, K, K4, Ks, T, W, stage_words, tab_words;
-};
+using namespace tm_rs;
 
 int rs_cus() {
   int dev = 0, cus = 0;
@@ -65,22 +58,6 @@ int rs_cus() {
       cus < 1)
     cus = 256;
   return cus;
-}
-
-bool rs_plan(int up, int down, int n_taps, int ch, RsPlan* pl) {
-  pl->up = up, pl->down = down, pl->n_taps = n_taps, pl->ch = ch;
-  pl->K = (n_taps + up - 1) / up;
-  pl->K4 = (pl->K + 3) / 4 * 4;
-  pl->Ks = 4 * (((pl->K + 3) / 4) | 1);
-  pl->tab_words = up * pl->Ks;
-  for (int T = kMaxTile; T >= 1; T >>= 1) {
-    pl->T = T;
-    pl->W = (int)(((i64)up - 1 + (i64)down * (T - 1)) / up) + pl->K4;
-    pl->stage_words = (3 + pl->W * ch + 3) / 4 * 4;  // up to 3 words before the first frame
-    if (sizeof(float) * ((size_t)pl->stage_words + pl->tab_words) <= (size_t)kLdsBytes)
-      return true;
-  }
-  return false;
 }
 
 // CH: the channel count where it is 1 or 2, else 0 (pl.ch at run time)
@@ -92,25 +69,19 @@ __global__ __launch_bounds__(kT) void k_rs_poly(const float* __restrict__ x, i64
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* stage = lds;
   float* tab = lds + pl.stage_words;
-  const int tid = threadIdx.x, up = pl.up, down = pl.down, K = pl.K;
+  const int tid = threadIdx.x;
   const int ch = CH ? CH : pl.ch;
   // once per workgroup; the first barrier of the loop publishes it
   for (int i = tid; i < pl.tab_words; i += kT) {
-    const int p = i / pl.Ks, v = i - p * pl.Ks;
-    const int m = p + up * (K - 1 - v);
-    tab[i] = (v < K && m < pl.n_taps) ? taps[m] : 0.0f;
+    const int m = rs_tab_src(pl, i);
+    tab[i] = m >= 0 ? taps[m] : 0.0f;
   }
   const i64 lo = start * ch, hi = (start + len) * ch;  // the live words of x
   const int n_el = pl.T * ch, steps = pl.K4 / 4;
   for (i64 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const i64 j0 = tile * pl.T;
-    const i64 c0 = (i64)down * j0 + (pl.n_taps - 1) / 2;
-    const i64 ih0 = c0 / up;
-    const int p0 = (int)(c0 - ih0 * up);
-    const i64 w0 = (start + ih0 - (K - 1)) * ch;  // first word of the span; may lie below 0
-    const i64 a0 = w0 & ~(i64)3;
-    const int shift = (int)(w0 - a0);
-    const int nq = (shift + pl.W * ch + 3) / 4;   // 16-byte pieces; 4 nq <= stage_words
+    const RsTile tl = rs_tile(pl, ch, start, tile);
+    const i64 j0 = tl.j0, a0 = tl.a0;
+    const int p0 = tl.p0, shift = tl.shift, nq = tl.nq;  // 4 nq <= stage_words
     __syncthreads();  // the previous tile's reads of stage
     for (int q0 = tid; q0 < nq; q0 += kInFlight * kT) {
       float4 r[kInFlight];
@@ -138,11 +109,10 @@ __global__ __launch_bounds__(kT) void k_rs_poly(const float* __restrict__ x, i64
     }
     __syncthreads();
     for (int e = tid; e < n_el; e += kT) {
-      const int o = e / ch, c = e - o * ch;
-      if (j0 + o >= n_out) break;  // e grows with o
-      const int xo = p0 + down * o, ao = xo / up, p = xo - ao * up;
-      const float* sp = stage + shift + ao * ch + c;
-      const float* h = tab + p * pl.Ks;
+      const RsElem el = rs_elem(pl, ch, p0, e);
+      if (j0 + el.o >= n_out) break;  // e grows with o
+      const float* sp = stage + rs_first_word(shift, ch, el);
+      const float* h = tab + rs_tab_row(pl, el.p);
       float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
       for (int i = 0; i < steps; ++i) {
         const float4 t = *reinterpret_cast<const float4*>(h + 4 * i);
@@ -164,27 +134,14 @@ extern "C" {
 int tomatis_resample_poly(const float* x, int64_t n_total, int64_t start, int64_t len,
                           int32_t channels, int32_t up, int32_t down, const float* taps,
                           int32_t n_taps, float* out, void* hs) {
-  if (!x || !taps || !out || n_total < 0 || start < 0 || len < 1 || len > n_total - start ||
-      n_taps < 1 || (n_taps & 1) == 0 || up < 1 || down < 1 || up == down || channels < 1 ||
-      channels > kMaxCh)
-    return TOMATIS_E_ARG;
-  for (int a = up, b = down;;) {  // gcd(up, down) == 1
-    const int r = a % b;
-    if (r == 0) {
-      if (b != 1) return TOMATIS_E_ARG;
-      break;
-    }
-    a = b, b = r;
-  }
-  const int big = up > down ? up : down;
-  if (big > kMaxRatio || (i64)down > (i64)kMaxDecim * up || n_taps > 20 * big + 1 ||
-      n_total > (int64_t)1 << 48)
-    return TOMATIS_E_UNSUPPORTED;
   RsPlan pl;
-  if (!rs_plan((int)up, (int)down, (int)n_taps, (int)channels, &pl)) return TOMATIS_E_UNSUPPORTED;
-  const i64 n_out = ((i64)len * up + down - 1) / down;
-  const i64 tiles = (n_out + pl.T - 1) / pl.T;
-  if (tiles > 0x7FFFFFFF) return TOMATIS_E_UNSUPPORTED;
+  i64 n_out = 0, tiles = 0;
+  switch (rs_check_args(x != nullptr, taps != nullptr, out != nullptr, n_total, start, len,
+                        channels, up, down, n_taps, &pl, &n_out, &tiles)) {
+    case kRsOk: break;
+    case kRsArg: return TOMATIS_E_ARG;
+    default: return TOMATIS_E_UNSUPPORTED;
+  }
   const i64 cap = (i64)rs_cus() * 4;  // resident workgroups, each builds its phase table once
   const unsigned groups = (unsigned)(tiles < cap ? tiles : cap);
   const size_t lds = sizeof(float) * ((size_t)pl.stage_words + pl.tab_words);

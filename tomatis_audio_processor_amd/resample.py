@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import check, lib, ptr, stream_handle
 
-MAX_RATIO = 512   # tm_resample.hip kMaxRatio: max(up, down)
+MAX_RATIO = 512   # csrc/tm_resample_plan.h kMaxRatio: max(up, down)
 MAX_DECIM = 8     # kMaxDecim: down <= MAX_DECIM up
 MAX_CH = 8        # kMaxCh
 MAX_TILE = 1024   # kMaxTile
@@ -78,9 +78,10 @@ def n_out(n: int, up: int, down: int) -> int:
 
 def outputs_per_workgroup(up: int, down: int, channels: int, n_taps=None,
                           lds_bytes: int = LDS_BYTES) -> int:
-    """T of tm_resample.hip's rs_plan: the largest power of two <= 1024
+    """T of csrc/tm_resample_plan.h's rs_plan: the largest power of two <= 1024
     consecutive output frames whose staged samples and phase table fit the LDS
-    budget.  ``lds_words`` gives the words it then uses."""
+    budget.  ``lds_words`` gives the words it then uses.  A mirror of the C
+    code, held to it by tests/test_resample_plan.py."""
     return _plan(up, down, channels, n_taps, lds_bytes)[0]
 
 
