@@ -864,6 +864,57 @@ int tomatis_resample_poly(const float* x, int64_t n_total, int64_t start, int64_
                           int32_t channels, int32_t up, int32_t down, const float* taps,
                           int32_t n_taps, float* out, void* hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * Device parameter recovery (SURVEY.md §8 row f11;
+ * src/reverse_engineer_params.py, src/verify_tilt_amplitude.py; tm_analysis.hip).
+ * x (the input) and y (the device's recording of it, aligned): float32 [n][2]
+ * interleaved stereo, device-resident; win: n_fft floats; frames and the n_fft
+ * limits as tomatis_an_spectra, F = 1 + (n - n_fft) / hop; n < n_fft: nothing is
+ * written.  The value of frame f and bin k < n_fft / 2 + 1 is, in float32,
+ *   d[f][k] = 20 log10f(|B_k| + 1e-12f) - 20 log10f(|A_k| + 1e-12f),
+ * A = rfft(win * power_mono(x)), B = rfft(win * power_mono(y)) of that frame:
+ * one transform of a + ib split into both spectra, the magnitudes hypotf as
+ * TOMATIS_AN_MAG's.  The two real bins, 0 and for even n_fft n_fft / 2, are
+ * float64 sums of the windowed samples rounded to float32 once (a power mono
+ * puts bin n_fft / 2 far under bin 0, and the logarithm turns the transform's
+ * rounding there into decibels).  No atomics anywhere: the same bits in every
+ * run and on every device.
+ * TOMATIS_E_ARG: a null pointer, hop < 1, a range outside
+ * 0 <= a <= b <= n_fft / 2 + 1, a bad frame list; TOMATIS_E_UNSUPPORTED: n_fft
+ * outside the limits; both before anything is read.
+ * ------------------------------------------------------------------------- */
+
+/* compute_tilt_index (reverse_engineer_params.py:62-76) of every frame:
+ * band_means[f] = (mean d[f][lo0:lo1], mean d[f][hi0:hi1]) as float64, each a
+ * float64 sum of the float32 values in a fixed order over the bin count.  The
+ * two ranges are independent and may overlap; an empty one gives NaN (numpy's
+ * mean of an empty slice).  rows, where not NULL, receives d: F * (n_fft/2+1)
+ * floats; band_means has the same bits with and without it.  band_means: F * 2
+ * doubles. */
+int tomatis_an_pair_tilt(const float* x, const float* y, int64_t n, int32_t n_fft, int32_t hop,
+                         int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1, const float* win,
+                         float* rows, double* band_means, void* hip_stream);
+
+/* doubles of workspace of tomatis_an_pair_diff_mean for a list of n_sel frames
+ * of n_bins = n_fft / 2 + 1 bins: one row of partial sums per slab of 16 list
+ * entries, then the list itself; 0 for a count outside [1, 2^31) or n_bins < 1. */
+int64_t tomatis_an_pair_diff_mean_work_doubles(int64_t n_sel, int32_t n_bins);
+
+/* np.mean(diffs, axis=0) of verify_tilt_amplitude.py:98-99: out[k] = the
+ * float64 mean of d[f][k] over the frames f of a list.  frames: n_sel int32 in
+ * HOST memory (as exc_host of tomatis_an_select), each in [0, F) and greater
+ * than the one before; it is checked here and then copied behind the partial
+ * sums in work on the stream.  frames NULL: every frame in order, and n_sel
+ * must be F.  The values are added in float64: in list order inside slabs of
+ * 16 consecutive list entries, then the slabs in ascending order, then one
+ * division by n_sel; the slab size is a constant of the source.  n_sel == 0:
+ * every out[k] is NaN, and work may be NULL.  work:
+ * tomatis_an_pair_diff_mean_work_doubles(n_sel, n_fft / 2 + 1) doubles; out:
+ * n_fft / 2 + 1 doubles. */
+int tomatis_an_pair_diff_mean(const float* x, const float* y, int64_t n, int32_t n_fft,
+                              int32_t hop, const float* win, const int32_t* frames,
+                              int32_t n_sel, double* work, double* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,12 @@ _SIGS = {
     "tomatis_an_frame_power_mean": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "tomatis_resample_poly": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
+    # parameter recovery
+    "tomatis_an_pair_tilt": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "tomatis_an_pair_diff_mean_work_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
+    "tomatis_an_pair_diff_mean": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P,
+                                            C.c_int32, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

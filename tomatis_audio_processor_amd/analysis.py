@@ -10,7 +10,9 @@ the reference functions:
 
 and, below them, the device pieces the two acceptance validators share
 (validate_layer1.py, verify_tomatis_15db_v2.py; row f9): the padded level grid,
-the gate scan, the anchored ratio rows and band energies, peak and float64 sum.
+the gate scan, the anchored ratio rows and band energies, peak and float64 sum;
+and the two the parameter-recovery tools share (reverse_engineer_params.py,
+verify_tilt_amplitude.py; row f11): ``pair_tilt`` and ``pair_diff_mean``.
 
 Everything per frame or per sample runs in ``libtomatis_hip.so``
 (``tm_analysis.hip``): framing, power-mono premix, window, real FFT (two real
@@ -415,6 +417,63 @@ def verify_spectra(xd, yd, n_fft, hop, anchor=None, bands=None, fused=True, win=
         check(L.tomatis_an_pair_band_energy(ptr(xd), ptr(yd), n, ch, n_fft, hop, *bands, ptr(win),
                                             ptr(be), hs), "an_pair_band_energy")
     return rows, be
+
+
+# ---------------------------------------------------------------------------
+# parameter recovery: the device pieces shared by
+# reverse_engineer_params.py and verify_tilt_amplitude.py
+# ---------------------------------------------------------------------------
+
+def pair_tilt(xd, yd, n_fft, hop, lo, hi, want_rows=False):
+    """Per frame of a resident stereo pair the means of d = 20 log10(|B| + EPS) -
+    20 log10(|A| + EPS) (A, B the power-mono spectra of x and y) over the bin
+    ranges ``lo`` = (lo0, lo1) and ``hi`` = (hi0, hi1): a float64 tensor [F, 2]
+    (tm_analysis.hip k_an_pair_tilt), and with ``want_rows`` the float32 rows
+    [F, n_fft/2+1] as well -> (band_means, rows or None)."""
+    _check_n_fft(n_fft)
+    torch = _torch()
+    n, ch = xd.shape
+    if ch != 2 or tuple(yd.shape) != (n, 2):
+        raise ValueError("x and y must be stereo and of one length")
+    F = max(0, _n_frames(n, n_fft, hop))
+    nb = n_fft // 2 + 1
+    win = torch.from_numpy(dsp.hann(n_fft)).cuda()
+    means = torch.empty((F, 2), dtype=torch.float64, device="cuda")
+    rows = torch.empty((F, nb), dtype=torch.float32, device="cuda") if want_rows else None
+    check(lib().tomatis_an_pair_tilt(ptr(xd), ptr(yd), n, n_fft, hop, *lo, *hi, ptr(win),
+                                     ptr(rows), ptr(means), stream_handle()), "an_pair_tilt")
+    return means, rows
+
+
+def pair_diff_mean(xd, yd, n_fft, hop, frames=None):
+    """The float64 mean over ``frames`` (ascending frame indices; default: every
+    frame) of the rows d of ``pair_tilt``: a float64 tensor [n_fft/2+1]
+    (tm_analysis.hip k_an_pair_diff_mean), NaN for an empty list.  The list stays
+    on the host: the library checks it and copies it behind its workspace."""
+    _check_n_fft(n_fft)
+    torch = _torch()
+    n, ch = xd.shape
+    if ch != 2 or tuple(yd.shape) != (n, 2):
+        raise ValueError("x and y must be stereo and of one length")
+    F = max(0, _n_frames(n, n_fft, hop))
+    nb = n_fft // 2 + 1
+    L = lib()
+    if frames is None:
+        fl, n_sel = None, F
+    else:
+        fl = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        n_sel = len(fl)
+        if n_sel == 0:
+            fl = np.zeros(1, np.int32)   # an empty list, not NULL (= every frame)
+    win = torch.from_numpy(dsp.hann(n_fft)).cuda()
+    work = torch.empty(max(1, int(L.tomatis_an_pair_diff_mean_work_doubles(n_sel, nb))),
+                       dtype=torch.float64, device="cuda")
+    out = torch.full((nb,), float("nan"), dtype=torch.float64, device="cuda")
+    check(L.tomatis_an_pair_diff_mean(ptr(xd), ptr(yd), n, n_fft, hop, ptr(win),
+                                      None if fl is None else fl.ctypes.data_as(C.c_void_p),
+                                      n_sel, ptr(work), ptr(out), stream_handle()),
+          "an_pair_diff_mean")
+    return out
 
 
 def sum_f64(t):

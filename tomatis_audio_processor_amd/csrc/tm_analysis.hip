@@ -20,6 +20,11 @@
 //       :307-354 ratio rows divided by their mean over an anchor band, :451-470
 //       band energies of input and output, :90 the DC mean
 //                                              -> k_an_verify, k_an_sum_part / _fold
+//   reverse_engineer_params / verify_tilt_amplitude (parameter recovery, row f11)
+//       src/reverse_engineer_params.py:118-143, src/verify_tilt_amplitude.py:74-99
+//       per frame the dB difference of the output's and the input's power-mono
+//       spectra, reduced to two band means or to a mean row over a frame list
+//                                              -> k_an_pair_tilt, k_an_pair_diff_mean
 //
 // Frames: f = 0 .. F-1 start at f*hop, F = 1 + (n - n_fft) / hop (every frame
 // lies inside the signal, as in all three reference loops).
@@ -53,6 +58,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -812,6 +818,157 @@ __global__ __launch_bounds__(kT) void k_an_verify(VerArgs V) {
 }
 
 // ---------------------------------------------------------------------------
+// Parameter recovery (reverse_engineer_params.py:118-143,
+// verify_tilt_amplitude.py:74-92): per frame and bin
+//   d[k] = 20 log10(|B_k| + EPS) - 20 log10(|A_k| + EPS),   float32,
+// A = rfft(win * power_mono(x)), B = rfft(win * power_mono(y)).  Both spectra
+// come from one transform of a + ib split as in k_an_verify, the magnitudes are
+// hypotf as TOMATIS_AN_MAG's.  The two real bins are taken from float64 sums
+// formed while the frame is staged, for k_an_spec_mean's reason: both signals
+// are power monos, so bin n / 2 lies far under bin 0 and the logarithm would
+// turn the transform's rounding there into decibels.
+//
+// pair_diff stages frame f, transforms, splits and hands every bin the thread
+// owns (t, t + kT, ...: ascending) to use(u, k, d).  It leaves buf and red in
+// use: a caller that stages another frame puts a barrier in between.
+// ---------------------------------------------------------------------------
+template <int M, bool BLUE, typename U>
+__device__ __forceinline__ void pair_diff(const SpecArgs& A, int f, float2* buf,
+                                          double (*red)[4], U&& use) {
+  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
+  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
+  const int64_t p0 = (int64_t)f * A.hop;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double re[4] = {0.0, 0.0, 0.0, 0.0};  // (a, bin 0), (a, n/2), (b, 0), (b, n/2)
+  for (int i = threadIdx.x; i < n; i += kT) {
+    const float w = A.win[i];
+    const float a = power_mono(A.x, p0 + i, 1.0f) * w;
+    const float b = power_mono(A.y, p0 + i, 1.0f) * w;
+    buf[i] = make_float2(a, b);
+    re[0] += (double)a;
+    re[1] += (i & 1) ? -(double)a : (double)a;
+    re[2] += (double)b;
+    re[3] += (i & 1) ? -(double)b : (double)b;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double v = re[j];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wv][j] = v;
+  }
+  __syncthreads();
+  lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) {
+    const int k = threadIdx.x + u * kT;
+    if (k < A.n_bins) {
+      float ma, mb;
+      if (k == 0 || 2 * k == n) {  // the real bins: the float64 sums, rounded once
+        const int j = k == 0 ? 0 : 1;
+        double va = 0.0, vb = 0.0;
+        for (int i = 0; i < kT / 64; ++i) {
+          va += red[i][j];
+          vb += red[i][2 + j];
+        }
+        ma = fabsf((float)va);
+        mb = fabsf((float)vb);
+      } else {
+        const float2 zk = buf[k], zm = buf[mirror(k, n)];
+        ma = hypotf(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+        mb = hypotf(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+      }
+      use(u, k, 20.0f * log10f(mb + kEps) - 20.0f * log10f(ma + kEps));
+    }
+  }
+}
+
+// compute_tilt_index's two band means of d (reverse_engineer_params.py:62-76),
+// one workgroup per frame: means[f] = (mean d[lo0:lo1], mean d[hi0:hi1]) as
+// float64, each a float64 sum of the float32 values in a fixed order (a
+// thread's bins ascending, a shuffle tree, the four waves in order: no atomics)
+// over the bin count; an empty range gives 0 / 0 = NaN, numpy's mean of an
+// empty slice.  The row is stored where rows is given; the sums do not depend
+// on it.
+struct TiltArgs {
+  SpecArgs S;     // out = rows [F][n_bins] or null, band = lo0, lo1, hi0, hi1
+  double* means;  // [F][2]
+};
+
+template <int M, bool BLUE>
+__global__ __launch_bounds__(kT) void k_an_pair_tilt(TiltArgs T) {
+  __shared__ float2 buf[M];
+  __shared__ double red[kT / 64][4];
+  __shared__ double sums[kT / 64][2];
+  const SpecArgs& A = T.S;
+  const int f = blockIdx.x;
+  float* o = A.out ? A.out + (int64_t)f * A.n_bins : nullptr;
+  double acc[2] = {0.0, 0.0};
+  pair_diff<M, BLUE>(A, f, buf, red, [&](int, int k, float d) {
+    if (o) o[k] = d;
+    if (k >= A.band[0] && k < A.band[1]) acc[0] += (double)d;
+    if (k >= A.band[2] && k < A.band[3]) acc[1] += (double)d;
+  });
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    double v = acc[j];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) sums[wv][j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int j = threadIdx.x;
+    double v = 0.0;
+    for (int i = 0; i < kT / 64; ++i) v += sums[i][j];
+    T.means[(int64_t)f * 2 + j] = v / (double)(A.band[2 * j + 1] - A.band[2 * j]);
+  }
+}
+
+// np.mean(diffs, axis=0) over a list of frames (verify_tilt_amplitude.py:98-99),
+// in float64 and in k_an_spec_mean's order: a workgroup owns kSlabFrames
+// consecutive list entries (a constant of the source) and walks them in order,
+// one float64 accumulator per owned bin in registers; the slab's sums go to
+// work[slab][bin] and k_an_spec_mean_fold adds the slabs in ascending order and
+// divides by the list's length.  frames == null: the list is 0, 1, 2, ...
+constexpr int kSlabFrames = 16;
+
+struct DiffMeanArgs {
+  SpecArgs S;
+  const int32_t* frames;  // [n_sel] or null
+  int n_sel;
+  double* work;  // [slabs][n_bins]
+};
+
+template <int M, bool BLUE>
+__global__ __launch_bounds__(kT) void k_an_pair_diff_mean(DiffMeanArgs D) {
+  __shared__ float2 buf[M];
+  __shared__ double red[kT / 64][4];
+  const SpecArgs& A = D.S;
+  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;
+  const int e0 = blockIdx.x * kSlabFrames;
+  const int e1 = min(e0 + kSlabFrames, D.n_sel);
+  double acc[kMaxUB];
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) acc[u] = 0.0;
+  for (int e = e0; e < e1; ++e) {
+    const int f = D.frames ? D.frames[e] : e;
+    pair_diff<M, BLUE>(A, f, buf, red, [&](int u, int, float d) { acc[u] += (double)d; });
+    __syncthreads();  // buf and red are written again for the next frame
+  }
+  double* o = D.work + (int64_t)blockIdx.x * A.n_bins;
+#pragma unroll
+  for (int u = 0; u < kMaxUB; ++u) {
+    const int k = threadIdx.x + u * kT;
+    if (k < A.n_bins) o[k] = acc[u];
+  }
+}
+
+__global__ void k_an_fill_f64(double* __restrict__ out, int n, double v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = v;
+}
+
+// ---------------------------------------------------------------------------
 // float64 sum of a float32 buffer (np.mean(y) of check_engineering,
 // verify_tomatis_15db_v2.py:90): kSumGroups partial sums over a fixed grid (a
 // constant of the source, not of the device), element i in group (i / kT) mod
@@ -1307,6 +1464,82 @@ int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_ff
   if (rc != TOMATIS_OK) return rc;
   hipLaunchKernelGGL(k_an_spec_mean_fold, dim3((nb + 63) / 64), dim3(64), 0, s,
                      (const double*)work, slabs, nb, (int)F, out);
+  return an_launch();
+}
+
+int tomatis_an_pair_tilt(const float* x, const float* y, int64_t n, int32_t n_fft, int32_t hop,
+                         int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1, const float* win,
+                         float* rows, double* band_means, void* hs) {
+  if (!x || !y || !win || !band_means || hop < 1 || n_fft < 1 || n < 0) return TOMATIS_E_ARG;
+  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
+  const int nb = n_fft / 2 + 1;
+  if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
+  if (n < n_fft) return TOMATIS_OK;
+  const int64_t F = 1 + (n - n_fft) / hop;
+  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)hs;
+  TiltArgs T{{x, y, win, nullptr, nullptr, nullptr, rows, n_fft, 0, hop, (int)F, nb, 1.0f,
+              {lo0, lo1, hi0, hi1}},
+             band_means};
+  int rc = dft_args(n_fft, s, &T.S);
+  if (rc != TOMATIS_OK) return rc;
+  const dim3 g((unsigned)F);
+  return dispatch_m(T.S, [&](auto m, auto b) {
+    hipLaunchKernelGGL((k_an_pair_tilt<decltype(m)::value, decltype(b)::value>), g, dim3(kT), 0,
+                       s, T);
+  });
+}
+
+int64_t tomatis_an_pair_diff_mean_work_doubles(int64_t n_sel, int32_t n_bins) {
+  if (n_sel < 1 || n_sel > INT32_MAX || n_bins < 1) return 0;
+  const int64_t slabs = (n_sel + kSlabFrames - 1) / kSlabFrames;
+  return slabs * (int64_t)n_bins + (n_sel + 1) / 2;  // the partial sums, then the list
+}
+
+int tomatis_an_pair_diff_mean(const float* x, const float* y, int64_t n, int32_t n_fft,
+                              int32_t hop, const float* win, const int32_t* frames,
+                              int32_t n_sel, double* work, double* out, void* hs) {
+  if (!x || !y || !win || !out || (!work && n_sel > 0) || hop < 1 || n_fft < 1 || n < 0 ||
+      n_sel < 0)
+    return TOMATIS_E_ARG;
+  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
+  if (n < n_fft) return TOMATIS_OK;
+  const int64_t F = 1 + (n - n_fft) / hop;
+  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  if (!frames && n_sel != F) return TOMATIS_E_ARG;
+  if (frames) {  // host memory: checked here, before anything is launched
+    for (int32_t e = 0; e < n_sel; ++e)
+      if (frames[e] < 0 || frames[e] >= F || (e && frames[e] <= frames[e - 1]))
+        return TOMATIS_E_ARG;
+  }
+  hipStream_t s = (hipStream_t)hs;
+  const int nb = n_fft / 2 + 1;
+  if (n_sel == 0) {  // numpy's mean over no rows
+    hipLaunchKernelGGL(k_an_fill_f64, dim3((nb + 255) / 256), dim3(256), 0, s, out, nb,
+                       std::numeric_limits<double>::quiet_NaN());
+    return an_launch();
+  }
+  const int slabs = (n_sel + kSlabFrames - 1) / kSlabFrames;
+  const int32_t* list = nullptr;
+  if (frames) {
+    int32_t* dl = reinterpret_cast<int32_t*>(work + (int64_t)slabs * nb);
+    const int rc = an_fail(hipMemcpyAsync(dl, frames, sizeof(int32_t) * (size_t)n_sel,
+                                          hipMemcpyHostToDevice, s));
+    if (rc != TOMATIS_OK) return rc;
+    list = dl;
+  }
+  DiffMeanArgs D{{x, y, win, nullptr, nullptr, nullptr, nullptr, n_fft, 0, hop, (int)F, nb, 1.0f},
+                 list, n_sel, work};
+  int rc = dft_args(n_fft, s, &D.S);
+  if (rc != TOMATIS_OK) return rc;
+  const dim3 g((unsigned)slabs);
+  rc = dispatch_m(D.S, [&](auto m, auto b) {
+    hipLaunchKernelGGL((k_an_pair_diff_mean<decltype(m)::value, decltype(b)::value>), g,
+                       dim3(kT), 0, s, D);
+  });
+  if (rc != TOMATIS_OK) return rc;
+  hipLaunchKernelGGL(k_an_spec_mean_fold, dim3((nb + 63) / 64), dim3(64), 0, s,
+                     (const double*)work, slabs, nb, n_sel, out);
   return an_launch();
 }
 
