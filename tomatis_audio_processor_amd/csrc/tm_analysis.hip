@@ -1,18 +1,22 @@
-// tm_analysis.hip — analysis spectra on the device.
+// tm_analysis.hip — analysis spectra on the device (SURVEY.md §8 rows f3/f4,
+// f8, f9, f11).
 //
 // The reference's validators and calibration tools run the same framing + real
-// FFT as the processors, then reduce over frames:
+// FFT as the processors, then reduce over bins or frames:
 //   compare_audio.stft_mag_avg                 src/compare_audio.py:12-24
-//       mean over frames of |rfft(win * x)|    -> k_an_spec<MAG>, k_an_frame_mean
+//       mean over frames of |rfft(win * x)|    -> k_an_spec_pair<MAG>, k_an_frame_mean
 //   layer2_analyze_eq.stft_logpower_median     src/layer2_analyze_eq.py:54-88
 //       frames with rms_dbfs(power_mono) > music_dbfs, median over frames of
 //       10 log10(|rfft(win * power_mono)|^2 + EPS)
 //                                              -> k_an_frame_r, k_an_select,
-//                                                 k_an_spec<LOGPOW>, median kernels
+//                                                 k_an_spec_pair<LOGPOW>, median kernels
 //   validate_layer1.compute_conditional_spectrum  src/validate_layer1.py:261-389
 //       stable C1/C2 frames with level >= threshold, median over frames of
 //       mean_c|Y_c| / max(mean_c|X_c|, 1e-10)  -> k_an_frame_r, k_an_select,
-//                                                 k_an_spec<RATIO>, median kernels
+//                                                 k_an_verify (rows, no anchor),
+//                                                 median kernels
+//   calibrate_to_baseline_v2.stft_band_tilt    src/calibrate_to_baseline_v2.py:17-31
+//       per frame two band sums of |rfft(win * power_mono)|^2  -> k_an_band_pair
 //   compare_to_baseline.avg_spectrum_db        src/compare_to_baseline.py:105-122
 //       mean over frames, in float64, of 10 log10(|rfft(win * power_mono)|^2 + EPS)
 //                                              -> k_an_spec_mean, k_an_spec_mean_fold
@@ -26,21 +30,25 @@
 //       spectra, reduced to two band means or to a mean row over a frame list
 //                                              -> k_an_pair_tilt, k_an_pair_diff_mean
 //
-// Frames: f = 0 .. F-1 start at f*hop, F = 1 + (n - n_fft) / hop (every frame
-// lies inside the signal, as in all three reference loops).
+// Frames: f = 0 .. F-1 start at f*hop, F = frame_count (every frame lies inside
+// the signal, as in all the reference loops).
 //
 // Layout and kernels (HBM-bound streaming work, no MFMA):
-//  * k_an_spec: one 256-thread workgroup per frame PAIR (MAG/LOGPOW: the two
-//    real frames are packed as a + ib into one complex FFT and split with
-//    Z[k] +- conj(Z[n-k])) or per frame (RATIO: x_c + i y_c per channel, so one
-//    complex FFT yields X_c and Y_c).  Frame staged in LDS (coalesced loads of
-//    the hop-strided PCM), Stockham autosort FFT in LDS (one radix-2 stage when
+//  * The six spectrum kernels share one frame front end (below, "The frame
+//    front end"): one 256-thread workgroup stages two real signals as a + ib in
+//    LDS (coalesced loads of the hop-strided PCM) -- a frame PAIR of one signal
+//    (k_an_spec_pair, k_an_band_pair, k_an_spec_mean) or one frame of an
+//    input/output pair (k_an_verify per channel, k_an_pair_tilt,
+//    k_an_pair_diff_mean) -- runs one complex FFT and splits it with
+//    Z[k] +- conj(Z[n-k]).  Stockham autosort FFT in LDS (one radix-2 stage when
 //    log2 n is odd, then radix-4 stages; every stage reads its butterflies into
 //    registers, barrier, writes, barrier), twiddles from a float table built in
 //    double precision once per size.  Any n_fft >= 16 (as np.fft.rfft): powers
 //    of two up to 16384 directly, other lengths up to 8192 by Bluestein's
 //    chirp-z over M = 2^k >= 2n - 1 in the same LDS buffer (tlds::lds_dft,
-//    tables per n from tm_host_dsp.h).  Output rows [F][n/2+1] f32.
+//    tables per n from tm_host_dsp.h).  Each kernel holds its own arithmetic
+//    and little else; sums over bins and frames are fixed-order (block_sums,
+//    slab_sums): no atomics, the same bits in every run.
 //  * k_an_frame_r: numpy's pairwise mean of m^2 per frame, restated exactly
 //    (128-sample leaves of 8 sequential chains, fixed 8-chain tree, perfect tree
 //    over leaves; correctly rounded sqrtf, -ffp-contract=off) so level gating is
@@ -54,6 +62,9 @@
 //    a per-bin pick.  numpy's even-count rule: fl32(fl32(v_lo + v_hi) / 2).
 //  * k_an_frame_mean: per-bin sequential float32 sum over frames then / F —
 //    numpy's axis-0 reduction order of np.stack(rows).mean(axis=0).
+//  * Host: every entry point checks its own arguments, then frame_count,
+//    bands_ok, a SpecArgs filled by name and completed by spec_args (M and the
+//    tables, cached per device by cached()), and a launch through dispatch_m.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -102,8 +113,28 @@ __global__ void k_an_twiddle(float2* tw, int n) {
   tw[t] = make_float2((float)c, (float)s);
 }
 
-std::mutex g_tw_mu;
-std::map<std::pair<int, int>, float2*> g_tw;  // (device, n) -> table (process lifetime)
+// Device tables are built once per (device, n) and kept for the life of the
+// process: cached() looks one up under the lock and, where it is missing, keeps
+// what build(&v) made (build frees whatever it allocated before it fails).
+template <typename V>
+using Cache = std::map<std::pair<int, int>, V>;
+std::mutex g_cache_mu;
+
+template <typename V, typename B>
+int cached(Cache<V>& cache, int n, V* out, B&& build) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return TOMATIS_E_HIP;
+  std::lock_guard<std::mutex> lk(g_cache_mu);
+  auto it = cache.find({dev, n});
+  if (it == cache.end()) {
+    V v{};
+    const int rc = build(&v);
+    if (rc != TOMATIS_OK) return rc;
+    it = cache.emplace(std::make_pair(dev, n), v).first;
+  }
+  *out = it->second;
+  return TOMATIS_OK;
+}
 
 template <typename T>
 int upload(const std::vector<T>& v, T** out) {
@@ -117,30 +148,25 @@ int upload(const std::vector<T>& v, T** out) {
   return TOMATIS_OK;
 }
 
+template <typename T, typename U>  // both tables or neither
+int upload2(const std::vector<T>& a, T** pa, const std::vector<U>& b, U** pb) {
+  int rc = upload(a, pa);
+  if (rc == TOMATIS_OK && (rc = upload(b, pb)) != TOMATIS_OK) (void)hipFree(*pa);
+  return rc;
+}
+
 struct Chirp {  // Bluestein tables for one n (tm_host_dsp.h bluestein_tables)
   float2* b = nullptr;
   float2* h = nullptr;
 };
-std::map<std::pair<int, int>, Chirp> g_chirp;  // (device, n), process lifetime
 
 int chirp_tables(int n, int M, Chirp* out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return TOMATIS_E_HIP;
-  std::lock_guard<std::mutex> lk(g_tw_mu);
-  auto it = g_chirp.find({dev, n});
-  if (it != g_chirp.end()) {
-    *out = it->second;
-    return TOMATIS_OK;
-  }
-  std::vector<float2> bf, hf;
-  thost::bluestein_tables(n, M, bf, hf);
-  Chirp c;
-  int rc = upload(bf, &c.b);
-  if (rc == TOMATIS_OK && (rc = upload(hf, &c.h)) != TOMATIS_OK) (void)hipFree(c.b);
-  if (rc != TOMATIS_OK) return rc;
-  g_chirp[{dev, n}] = c;
-  *out = c;
-  return TOMATIS_OK;
+  static Cache<Chirp> cache;
+  return cached(cache, n, out, [&](Chirp* c) -> int {
+    std::vector<float2> bf, hf;
+    thost::bluestein_tables(n, M, bf, hf);
+    return upload2(bf, &c->b, hf, &c->h);
+  });
 }
 
 struct PwProg {  // numpy's pairwise tree over one frame length
@@ -148,53 +174,32 @@ struct PwProg {  // numpy's pairwise tree over one frame length
   int16_t* prog = nullptr;
   int n_leaf = 0, n_prog = 0;
 };
-std::map<std::pair<int, int>, PwProg> g_pw;  // (device, n), process lifetime
 
 int pw_program(int n, PwProg* out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return TOMATIS_E_HIP;
-  std::lock_guard<std::mutex> lk(g_tw_mu);
-  auto it = g_pw.find({dev, n});
-  if (it != g_pw.end()) {
-    *out = it->second;
-    return TOMATIS_OK;
-  }
-  std::vector<int2> lv;
-  std::vector<int16_t> prog;
-  thost::pw_program(n, lv, prog);
-  if ((int)lv.size() > kPwMax) return TOMATIS_E_UNSUPPORTED;
-  PwProg q;
-  q.n_leaf = (int)lv.size();
-  q.n_prog = (int)prog.size();
-  int rc = upload(lv, &q.leaf);
-  if (rc == TOMATIS_OK && (rc = upload(prog, &q.prog)) != TOMATIS_OK) (void)hipFree(q.leaf);
-  if (rc != TOMATIS_OK) return rc;
-  g_pw[{dev, n}] = q;
-  *out = q;
-  return TOMATIS_OK;
+  static Cache<PwProg> cache;
+  return cached(cache, n, out, [&](PwProg* q) -> int {
+    std::vector<int2> lv;
+    std::vector<int16_t> prog;
+    thost::pw_program(n, lv, prog);
+    if ((int)lv.size() > kPwMax) return TOMATIS_E_UNSUPPORTED;
+    q->n_leaf = (int)lv.size();
+    q->n_prog = (int)prog.size();
+    return upload2(lv, &q->leaf, prog, &q->prog);
+  });
 }
 
 int twiddles(int n, hipStream_t s, const float2** out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return TOMATIS_E_HIP;
-  std::lock_guard<std::mutex> lk(g_tw_mu);
-  auto it = g_tw.find({dev, n});
-  if (it != g_tw.end()) {
-    *out = it->second;
-    return TOMATIS_OK;
-  }
-  float2* p = nullptr;
-  if (hipMalloc(&p, sizeof(float2) * n) != hipSuccess) return TOMATIS_E_NOMEM;
-  hipLaunchKernelGGL(k_an_twiddle, dim3((n + 255) / 256), dim3(256), 0, s, p, n);
-  int rc = an_launch();
-  if (rc == TOMATIS_OK) rc = an_fail(hipStreamSynchronize(s));  // visible to every stream
-  if (rc != TOMATIS_OK) {
-    (void)hipFree(p);
+  static Cache<const float2*> cache;
+  return cached(cache, n, out, [&](const float2** tw) -> int {
+    float2* p = nullptr;
+    if (hipMalloc(&p, sizeof(float2) * n) != hipSuccess) return TOMATIS_E_NOMEM;
+    hipLaunchKernelGGL(k_an_twiddle, dim3((n + 255) / 256), dim3(256), 0, s, p, n);
+    int rc = an_launch();
+    if (rc == TOMATIS_OK) rc = an_fail(hipStreamSynchronize(s));  // visible to every stream
+    if (rc != TOMATIS_OK) (void)hipFree(p);
+    else *tw = p;
     return rc;
-  }
-  g_tw[{dev, n}] = p;
-  *out = p;
-  return TOMATIS_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -372,17 +377,17 @@ using tlds::lds_dft;
 // ---------------------------------------------------------------------------
 // spectra
 // ---------------------------------------------------------------------------
-struct SpecArgs {
-  const float* x;
-  const float* y;
-  const float* win;
-  const float2* tw;  // exp(-2 pi i t / M)
-  const float2* bb;  // Bluestein chirp b (n_fft), BLUE kernels only
-  const float2* bh;  // Bluestein kernel spectrum H (M)
-  float* out;
-  int n_fft, M, hop, n_frames, n_bins;
-  float sc;
-  int band[4];  // TOMATIS_AN_BAND: bins [band0, band1) and [band2, band3)
+struct SpecArgs {  // filled by name, then completed by spec_args (host side below)
+  const float* x = nullptr;
+  const float* y = nullptr;
+  const float* win = nullptr;
+  const float2* tw = nullptr;  // exp(-2 pi i t / M)
+  const float2* bb = nullptr;  // Bluestein chirp b (n_fft), BLUE kernels only
+  const float2* bh = nullptr;  // Bluestein kernel spectrum H (M)
+  float* out = nullptr;
+  int n_fft = 0, M = 0, hop = 0, n_frames = 0, n_bins = 0;
+  float sc = 1.0f;
+  int band[4] = {0, 0, 0, 0};  // bins [band0, band1) and [band2, band3)
 };
 
 template <int SIG>  // TOMATIS_AN_SIG_RAW (ch 1) / TOMATIS_AN_SIG_POWER_MONO (ch 2)
@@ -391,61 +396,162 @@ __device__ __forceinline__ float sig_at(const float* __restrict__ x, int64_t p, 
   else return x[p] * sc;
 }
 
-// DFT bin mirrored for the two-real-frames split: (n - k) mod n
+// ---------------------------------------------------------------------------
+// The frame front end: what every spectrum kernel does around its own
+// arithmetic.  A kernel stages two real signals as a + ib (stage_pair),
+// transforms (lds_dft), and walks the bins it owns (owned_bins), taking both
+// spectra of a bin from split_pair; sums over bins go through block_sums.  The
+// helpers fix every order a result depends on: a thread's bins ascending, the
+// shuffle offsets 32 -> 1, the waves 0..3, float64 adds of float32 values.
+// ---------------------------------------------------------------------------
+template <int M>
+constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
+
+// fn(u, k) for the bins k = t, t + kT, ... below n_bins; u counts them from 0
+template <int M, typename F>
+__device__ __forceinline__ void owned_bins(int n_bins, F&& fn) {
+#pragma unroll
+  for (int u = 0; u < kMaxUB<M>; ++u) {
+    const int k = threadIdx.x + u * kT;
+    // k < n_bins, with the uniform part of it on the scalar side
+    if ((int)threadIdx.x < n_bins - u * kT) fn(u, k);
+  }
+}
+
+__device__ __forceinline__ bool in_range(int k, int lo, int hi) { return k >= lo && k < hi; }
+__device__ __forceinline__ float power(float2 z) { return z.x * z.x + z.y * z.y; }
+// 10 log10(re^2 + im^2 + EPS), float32 (layer2_analyze_eq.py:78-79)
+__device__ __forceinline__ float logpow_db(float2 z) { return 10.0f * log10f(power(z) + kEps); }
+
+// DFT bin mirrored for the two-real-signals split: (n - k) mod n
 __device__ __forceinline__ int mirror(int k, int n) { return k == 0 ? 0 : n - k; }
 
-// MAG / LOGPOW: workgroup per frame pair (2g, 2g+1) packed as a + ib
+// bin k of both spectra of Z = dft(a + ib):
+//   A = (Z[k] + conj Z[n-k]) / 2, B = (Z[k] - conj Z[n-k]) / 2i
+struct BinPair {
+  float2 a, b;
+};
+__device__ __forceinline__ BinPair split_pair(const float2* buf, int k, int n) {
+  const float2 zk = buf[k], zm = buf[mirror(k, n)];
+  return {make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)),
+          make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x))};
+}
+
+// Fixed-order block sums of J values per thread: a shuffle tree inside each wave,
+// lane 0 writes red[wave][j], barrier; wave_total then adds waves 0..3 in order.
+// No atomics: the same bits in every run.
+template <int J, typename T>
+__device__ __forceinline__ void block_sums(const T (&acc)[J], T (*red)[J]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    T v = acc[j];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wv][j] = v;
+  }
+  __syncthreads();
+}
+template <int J, typename T>
+__device__ __forceinline__ T wave_total(const T (*red)[J], int j) {
+  T v = 0;
+  for (int i = 0; i < kT / 64; ++i) v += red[i][j];
+  return v;
+}
+
+// buf[i] = (a_of(i) * win[i], has_b ? b_of(i) * win[i] : 0) for i < n, then a
+// barrier.  REAL64 also leaves in red the float64 sums of the windowed samples
+// with signs +1 and (-1)^i, that is the two real-valued bins 0 and (n even)
+// n / 2 of both signals: (a, bin 0), (a, n/2), (b, 0), (b, n/2).  A real bin
+// passes through zero, where a logarithm turns the transform's rounding
+// (relative to the frame's largest bin) into decibels, and a positive signal
+// such as the power mono puts n / 2 some 50 dB under bin 0; kernels that take
+// logarithms of such signals read these bins from real_bins instead.
+template <bool REAL64, typename FA, typename FB>
+__device__ __forceinline__ void stage_pair(float2* buf, double (*red)[4], int n,
+                                           const float* __restrict__ win, FA&& a_of, FB&& b_of,
+                                           bool has_b = true) {
+  double re[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < n; i += kT) {
+    const float w = win[i];
+    const float a = a_of(i) * w;
+    const float b = has_b ? b_of(i) * w : 0.f;
+    buf[i] = make_float2(a, b);
+    if constexpr (REAL64) {
+      re[0] += (double)a;
+      re[1] += (i & 1) ? -(double)a : (double)a;
+      re[2] += (double)b;
+      re[3] += (i & 1) ? -(double)b : (double)b;
+    }
+  }
+  if constexpr (REAL64) block_sums(re, red);
+  else __syncthreads();
+}
+
+// which real bin k is of a length-n transform: 0 (bin 0), 1 (bin n / 2), else -1
+__device__ __forceinline__ int real_bin(int k, int n) { return k == 0 ? 0 : 2 * k == n ? 1 : -1; }
+// stage_pair<true>'s real bin j of (a, b): the float64 sums, rounded once
+__device__ __forceinline__ float2 real_bins(const double (*red)[4], int j) {
+  return make_float2((float)wave_total(red, j), (float)wave_total(red, 2 + j));
+}
+
+// frames f0 and f0 + 1 of x packed as a + ib; past the last frame b = 0
+template <bool REAL64, int SIG>
+__device__ __forceinline__ void stage_frames(const SpecArgs& A, int n, int f0, bool has1,
+                                             float2* buf, double (*red)[4]) {
+  const int64_t p0 = (int64_t)f0 * A.hop, p1 = (int64_t)(f0 + 1) * A.hop;
+  stage_pair<REAL64>(
+      buf, red, n, A.win, [&](int i) { return sig_at<SIG>(A.x, p0 + i, A.sc); },
+      [&](int i) { return sig_at<SIG>(A.x, p1 + i, A.sc); }, has1);
+}
+
+// A float64 mean over many frames: a workgroup owns per_slab consecutive items
+// (a constant of the source: neither the device nor the grid changes a bit of
+// the result) and walks them in order; a thread keeps one float64 accumulator
+// per bin it owns (registers: the LDS holds the transform) and item(e, acc) adds
+// item e's values.  The slab's sums go to work[slab][bin]; k_an_spec_mean_fold
+// adds the slabs in ascending order.
+template <int M, typename F>
+__device__ __forceinline__ void slab_sums(int per_slab, int n_items, int n_bins,
+                                          double* __restrict__ work, F&& item) {
+  double acc[kMaxUB<M>];
+#pragma unroll
+  for (int u = 0; u < kMaxUB<M>; ++u) acc[u] = 0.0;
+  const int e0 = blockIdx.x * per_slab, e1 = min(e0 + per_slab, n_items);
+  for (int e = e0; e < e1; ++e) {
+    item(e, acc);
+    __syncthreads();  // the item's LDS is written again for the next one
+  }
+  double* o = work + (int64_t)blockIdx.x * n_bins;
+  owned_bins<M>(n_bins, [&](int u, int k) { o[k] = acc[u]; });
+}
+
+// MAG / LOGPOW: workgroup per frame pair (2g, 2g+1)
 template <int KIND, int SIG, int M, bool BLUE>
 __global__ __launch_bounds__(kT) void k_an_spec_pair(SpecArgs A) {
   __shared__ float2 buf[M];
-  const int f0 = blockIdx.x * 2, f1 = f0 + 1;
-  const bool has1 = f1 < A.n_frames;
+  const int f0 = blockIdx.x * 2;
+  const bool has1 = f0 + 1 < A.n_frames;
   const int n = BLUE ? A.n_fft : M;  // constant for powers of two
-  const int64_t p0 = (int64_t)f0 * A.hop, p1 = (int64_t)f1 * A.hop;
-  for (int i = threadIdx.x; i < n; i += kT) {
-    const float w = A.win[i];
-    const float a = sig_at<SIG>(A.x, p0 + i, A.sc) * w;
-    const float b = has1 ? sig_at<SIG>(A.x, p1 + i, A.sc) * w : 0.f;
-    buf[i] = make_float2(a, b);
-  }
-  __syncthreads();
+  stage_frames<false, SIG>(A, n, f0, has1, buf, nullptr);
   lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
   float* o0 = A.out + (int64_t)f0 * A.n_bins;
-  float* o1 = A.out + (int64_t)f1 * A.n_bins;
-  for (int k = threadIdx.x; k < A.n_bins; k += kT) {
-    const float2 zk = buf[k], zm = buf[mirror(k, n)];
-    // A = (Z[k] + conj Z[n-k]) / 2, B = (Z[k] - conj Z[n-k]) / 2i
-    const float2 fa = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-    const float2 fb = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+  float* o1 = o0 + A.n_bins;
+  owned_bins<M>(A.n_bins, [&](int, int k) {
+    const BinPair z = split_pair(buf, k, n);
     if constexpr (KIND == TOMATIS_AN_MAG) {
-      o0[k] = hypotf(fa.x, fa.y);
-      if (has1) o1[k] = hypotf(fb.x, fb.y);
-    } else {  // 10 log10(re^2 + im^2 + EPS), float32 (layer2_analyze_eq.py:78-79)
-      const float pa = fa.x * fa.x + fa.y * fa.y;
-      o0[k] = 10.0f * log10f(pa + kEps);
-      if (has1) {
-        const float pb = fb.x * fb.x + fb.y * fb.y;
-        o1[k] = 10.0f * log10f(pb + kEps);
-      }
+      o0[k] = hypotf(z.a.x, z.a.y);
+      if (has1) o1[k] = hypotf(z.b.x, z.b.y);
+    } else {
+      o0[k] = logpow_db(z.a);
+      if (has1) o1[k] = logpow_db(z.b);
     }
-  }
+  });
 }
 
 // Mean log-power spectrum (avg_spectrum_db, compare_to_baseline.py:105-122): the
 // LOGPOW value of k_an_spec_pair, summed over frames in float64 instead of
-// stored.  A workgroup owns kSlabPairs consecutive frame pairs (a constant of
-// the source: neither the device nor the grid changes a bit of the result) and
-// walks them in frame order; a thread keeps one float64 accumulator per bin it
-// owns (bins t, t + kT, ...: registers, the LDS holds the transform) and adds
-// frame 2g, then frame 2g + 1 where it exists.  The slab's sums go to
-// work[slab][bin]; k_an_spec_mean_fold adds the slabs in ascending order.
-// The two real-valued bins, 0 and (n even) n / 2, are plain sums of the windowed
-// samples with signs +1 and (-1)^i.  A real bin passes through zero, where its
-// logarithm turns the transform's rounding (relative to the frame's largest
-// bin) into decibels, and a positive signal such as the power mono puts n / 2
-// some 50 dB under bin 0; both are therefore summed in float64 while the frame
-// is staged (a fixed shuffle tree, then the four waves in order) and rounded to
-// float32 once.
+// stored: slab_sums over kSlabPairs frame pairs, frame 2g added, then frame
+// 2g + 1 where it exists; the two real bins from the float64 sums.
 constexpr int kSlabPairs = 8;
 
 struct MeanArgs {
@@ -456,74 +562,25 @@ struct MeanArgs {
 template <int SIG, int M, bool BLUE>
 __global__ __launch_bounds__(kT) void k_an_spec_mean(MeanArgs B) {
   __shared__ float2 buf[M];
-  const SpecArgs& A = B.S;
-  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
-  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
-  const int n_pairs = (A.n_frames + 1) / 2;
-  const int g0 = blockIdx.x * kSlabPairs;
-  const int g1 = min(g0 + kSlabPairs, n_pairs);
   __shared__ double red[kT / 64][4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double acc[kMaxUB];
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) acc[u] = 0.0;
-  for (int g = g0; g < g1; ++g) {
-    const int f0 = 2 * g, f1 = f0 + 1;
-    const bool has1 = f1 < A.n_frames;
-    const int64_t p0 = (int64_t)f0 * A.hop, p1 = (int64_t)f1 * A.hop;
-    double re[4] = {0.0, 0.0, 0.0, 0.0};  // (frame a, bin 0), (a, n/2), (b, 0), (b, n/2)
-    for (int i = threadIdx.x; i < n; i += kT) {
-      const float w = A.win[i];
-      const float a = sig_at<SIG>(A.x, p0 + i, A.sc) * w;
-      const float b = has1 ? sig_at<SIG>(A.x, p1 + i, A.sc) * w : 0.f;
-      buf[i] = make_float2(a, b);
-      const double sa = (i & 1) ? -(double)a : (double)a, sb = (i & 1) ? -(double)b : (double)b;
-      re[0] += (double)a;
-      re[1] += sa;
-      re[2] += (double)b;
-      re[3] += sb;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double v = re[j];
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane == 0) red[wv][j] = v;
-    }
-    __syncthreads();
+  const SpecArgs& A = B.S;
+  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
+  slab_sums<M>(kSlabPairs, (A.n_frames + 1) / 2, A.n_bins, B.work, [&](int g, auto& acc) {
+    const int f0 = 2 * g;
+    const bool has1 = f0 + 1 < A.n_frames;
+    stage_frames<true, SIG>(A, n, f0, has1, buf, red);
     lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
-#pragma unroll
-    for (int u = 0; u < kMaxUB; ++u) {
-      const int k = threadIdx.x + u * kT;
-      if (k < A.n_bins) {
-        const float2 zk = buf[k], zm = buf[mirror(k, n)];
-        float2 fa = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        float2 fb = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-        if (k == 0 || 2 * k == n) {  // the real bins: the float64 sums, rounded once
-          const int j = k == 0 ? 0 : 1;
-          double va = 0.0, vb = 0.0;
-          for (int i = 0; i < kT / 64; ++i) {
-            va += red[i][j];
-            vb += red[i][2 + j];
-          }
-          fa = make_float2((float)va, 0.f);
-          fb = make_float2((float)vb, 0.f);
-        }
-        const float pa = fa.x * fa.x + fa.y * fa.y;
-        acc[u] += (double)(10.0f * log10f(pa + kEps));
-        if (has1) {  // an odd count's last frame has no partner: nothing is added for it
-          const float pb = fb.x * fb.x + fb.y * fb.y;
-          acc[u] += (double)(10.0f * log10f(pb + kEps));
-        }
+    owned_bins<M>(A.n_bins, [&](int u, int k) {
+      BinPair z = split_pair(buf, k, n);
+      if (const int j = real_bin(k, n); j >= 0) {
+        const float2 r = real_bins(red, j);
+        z = {make_float2(r.x, 0.f), make_float2(r.y, 0.f)};
       }
-    }
-    __syncthreads();  // buf and red are written again for the next pair
-  }
-  double* o = B.work + (int64_t)blockIdx.x * A.n_bins;
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) {
-    const int k = threadIdx.x + u * kT;
-    if (k < A.n_bins) o[k] = acc[u];
-  }
+      acc[u] += (double)logpow_db(z.a);
+      // an odd count's last frame has no partner: nothing is added for it
+      if (has1) acc[u] += (double)logpow_db(z.b);
+    });
+  });
 }
 
 // out[k] = (work[0][k] + work[1][k] + ...) / max(n_frames, 1): one chain per bin
@@ -549,32 +606,22 @@ __global__ __launch_bounds__(64) void k_an_spec_mean_fold(const double* __restri
 // BAND (stft_band_tilt, calibrate_to_baseline_v2.py:17-31): per frame of the
 // pair the float32 power re^2 + im^2 of rfft(win * power_mono) summed over two
 // bin ranges, each on its own (the reference takes any two masks: the ranges
-// may overlap or be empty); workgroup per frame pair as k_an_spec_pair, block
-// reduction.
+// may overlap or be empty); workgroup per frame pair as k_an_spec_pair.
 template <int M, bool BLUE>
 __global__ __launch_bounds__(kT) void k_an_band_pair(SpecArgs A) {
   __shared__ float2 buf[M];
-  const int N = BLUE ? A.n_fft : M;
   __shared__ float red[kT / 64][4];
-  const int f0 = blockIdx.x * 2, f1 = f0 + 1;
-  const bool has1 = f1 < A.n_frames;
-  const int64_t p0 = (int64_t)f0 * A.hop, p1 = (int64_t)f1 * A.hop;
-  for (int i = threadIdx.x; i < N; i += kT) {
-    const float w = A.win[i];
-    const float a = power_mono(A.x, p0 + i, A.sc) * w;
-    const float b = has1 ? power_mono(A.x, p1 + i, A.sc) * w : 0.f;
-    buf[i] = make_float2(a, b);
-  }
-  __syncthreads();
-  lds_dft<M, BLUE>(buf, N, A.tw, A.bb, A.bh);
+  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
+  const int f0 = blockIdx.x * 2;
+  const bool has1 = f0 + 1 < A.n_frames;
+  stage_frames<false, TOMATIS_AN_SIG_POWER_MONO>(A, n, f0, has1, buf, nullptr);
+  lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};  // (frame a, band lo), (a, hi), (b, lo), (b, hi)
-  for (int k = threadIdx.x; k < A.n_bins; k += kT) {
-    const bool lo = k >= A.band[0] && k < A.band[1], hi = k >= A.band[2] && k < A.band[3];
-    if (!lo && !hi) continue;
-    const float2 zk = buf[k], zm = buf[mirror(k, N)];
-    const float2 fa = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-    const float2 fb = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-    const float pa = fa.x * fa.x + fa.y * fa.y, pb = fb.x * fb.x + fb.y * fb.y;
+  owned_bins<M>(A.n_bins, [&](int, int k) {
+    const bool lo = in_range(k, A.band[0], A.band[1]), hi = in_range(k, A.band[2], A.band[3]);
+    if (!lo && !hi) return;
+    const BinPair z = split_pair(buf, k, n);
+    const float pa = power(z.a), pb = power(z.b);
     if (lo) {
       acc[0] += pa;
       acc[2] += pb;
@@ -583,23 +630,15 @@ __global__ __launch_bounds__(kT) void k_an_band_pair(SpecArgs A) {
       acc[1] += pa;
       acc[3] += pb;
     }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[w][j] = v;
-  }
-  __syncthreads();
+  });
+  block_sums(acc, red);
   if (threadIdx.x < 4) {
-    float v = 0.f;
-    for (int i = 0; i < kT / 64; ++i) v += red[i][threadIdx.x];
     const int j = threadIdx.x;
-    if (j < 2) A.out[(int64_t)f0 * 2 + j] = v;
-    else if (has1) A.out[(int64_t)f1 * 2 + (j - 2)] = v;
+    const float v = wave_total(red, j);
+    if (j < 2 || has1) A.out[(int64_t)f0 * 2 + j] = v;  // out[F][2]: j >= 2 is frame f0 + 1
   }
 }
+
 
 // Gate-calibration grid (calibrate_to_baseline_v2.py:84-109 simulate_state,
 // :241-265 the search): one lane per candidate runs the standard automaton
@@ -650,80 +689,34 @@ __global__ __launch_bounds__(256) void k_cal_gate_grid(const float* __restrict__
   out[2 * c + 1] = sw;
 }
 
-// RATIO: workgroup per frame; per channel one FFT of x_c + i y_c
-template <int CH, int M, bool BLUE>
-__global__ __launch_bounds__(kT) void k_an_spec_ratio(SpecArgs A) {
-  __shared__ float2 buf[M];
-  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
-  const int f = blockIdx.x;
-  const int n = BLUE ? A.n_fft : M;  // constant for powers of two
-  const int64_t p0 = (int64_t)f * A.hop;
-  float ax[kMaxUB], ay[kMaxUB];
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) ax[u] = ay[u] = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    for (int i = threadIdx.x; i < n; i += kT) {
-      const float w = A.win[i];
-      const int64_t q = (p0 + i) * CH + c;
-      buf[i] = make_float2(A.x[q] * w, A.y[q] * w);
-    }
-    __syncthreads();
-    lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
-#pragma unroll
-    for (int u = 0; u < kMaxUB; ++u) {
-      const int k = threadIdx.x + u * kT;
-      if (k < A.n_bins) {
-        const float2 zk = buf[k], zm = buf[mirror(k, n)];
-        const float xr = 0.5f * (zk.x + zm.x), xi = 0.5f * (zk.y - zm.y);
-        const float yr = 0.5f * (zk.y + zm.y), yi = -0.5f * (zk.x - zm.x);
-        ax[u] = ax[u] + hypotf(xr, xi);  // X += |rfft(x_c * win)|
-        ay[u] = ay[u] + hypotf(yr, yi);
-      }
-    }
-    __syncthreads();  // buf reused by the next channel
-  }
-  float* o = A.out + (int64_t)f * A.n_bins;
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) {
-    const int k = threadIdx.x + u * kT;
-    if (k < A.n_bins) {
-      float X = (CH == 1) ? ax[u] : ax[u] * 0.5f;  // X /= ch
-      const float Y = (CH == 1) ? ay[u] : ay[u] * 0.5f;
-      X = fmaxf(X, 1e-10f);                        // np.maximum(X, 1e-10)
-      o[k] = Y / X;
-    }
-  }
-}
-
-// Acceptance validator v2 (verify_tomatis_15db_v2.py): the per-frame work of its
-// sections C and D on an input/output pair, one workgroup per frame and one
-// transform of x_c + i y_c per channel, as k_an_spec_ratio.
-//   ROWS  (:307-354)  ratio[k] = mean_c|Y_c| / max(mean_c|X_c|, 1e-10) exactly as
-//     k_an_spec_ratio forms it, then g = mean(ratio[a0:a1]) and the row stored as
-//     ratio / g when the anchor range is not empty and g > 0, else as it is (the
-//     reference's np.mean of an empty slice is NaN, and NaN > 0 is false).
+// Input/output pairs, one workgroup per frame and one transform of x_c + i y_c
+// per channel: TOMATIS_AN_RATIO (compute_conditional_spectrum) and the per-frame
+// work of sections C and D of the acceptance validator v2
+// (verify_tomatis_15db_v2.py).
+//   ROWS  (:307-354)  ratio[k] = mean_c|Y_c| / max(mean_c|X_c|, 1e-10).  With
+//     ANCHOR, g = mean(ratio[a0:a1]) and the row is stored as ratio / g when g > 0,
+//     else as it is (the reference's np.mean of an empty slice is NaN, and
+//     NaN > 0 is false).  The host leaves ANCHOR out where the range is empty:
+//     the row is stored as it is without the reduction and its barrier.
 //   BANDS (:451-470)  P_x[k] = mean_c |X_c[k]|^2 (re^2 + im^2 in float32), P_y
 //     likewise; bands[f] = (sum P_x[lo), sum P_x[hi), sum P_y[lo), sum P_y[hi)),
 //     the two ranges independent and possibly empty as in k_an_band_pair.
-// The row stays in registers after the split (bins t, t + kT, ...); the anchor
-// sum and the four band sums go through one fixed-order block reduction (a
-// thread's bins ascending, a shuffle tree, the four waves in order): no atomics,
-// the same bits in every run, and the same bits whether a launch forms the rows,
-// the bands or both.
+// The row stays in registers after the split; the anchor sum and the four band
+// sums go through one block_sums: the same bits in every run, and the same bits
+// whether a launch forms the rows, the bands or both.
 struct VerArgs {
   SpecArgs S;    // out = rows [F][n_bins] (ROWS), band = lo0, lo1, hi0, hi1 (BANDS)
   float* bands;  // [F][4]
   int a0, a1;    // anchor bins [a0, a1)
 };
 
-template <int CH, int M, bool BLUE, bool ROWS, bool BANDS>
+template <int CH, int M, bool BLUE, bool ROWS, bool BANDS, bool ANCHOR>
 __global__ __launch_bounds__(kT) void k_an_verify(VerArgs V) {
+  static_assert((ROWS || BANDS) && (ROWS || !ANCHOR), "ANCHOR scales the rows");
   __shared__ float2 buf[M];
   __shared__ float red[kT / 64][5];
   const SpecArgs& A = V.S;
-  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
-  constexpr int kUR = ROWS ? kMaxUB : 1, kUP = BANDS ? kMaxUB : 1;
+  constexpr int kUR = ROWS ? kMaxUB<M> : 1, kUP = BANDS ? kMaxUB<M> : 1;
   const int f = blockIdx.x;
   const int n = BLUE ? A.n_fft : M;  // constant for powers of two
   const int64_t p0 = (int64_t)f * A.hop;
@@ -734,86 +727,57 @@ __global__ __launch_bounds__(kT) void k_an_verify(VerArgs V) {
   for (int u = 0; u < kUP; ++u) px[u] = py[u] = 0.f;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
-    for (int i = threadIdx.x; i < n; i += kT) {
-      const float w = A.win[i];
-      const int64_t q = (p0 + i) * CH + c;
-      buf[i] = make_float2(A.x[q] * w, A.y[q] * w);
-    }
-    __syncthreads();
+    stage_pair<false>(
+        buf, nullptr, n, A.win, [&](int i) { return A.x[(p0 + i) * CH + c]; },
+        [&](int i) { return A.y[(p0 + i) * CH + c]; });
     lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
-#pragma unroll
-    for (int u = 0; u < kMaxUB; ++u) {
-      const int k = threadIdx.x + u * kT;
-      if (k < A.n_bins) {
-        const float2 zk = buf[k], zm = buf[mirror(k, n)];
-        const float xr = 0.5f * (zk.x + zm.x), xi = 0.5f * (zk.y - zm.y);
-        const float yr = 0.5f * (zk.y + zm.y), yi = -0.5f * (zk.x - zm.x);
-        if constexpr (ROWS) {
-          ax[u] = ax[u] + hypotf(xr, xi);  // X += |rfft(x_c * win)|
-          ay[u] = ay[u] + hypotf(yr, yi);
-        }
-        if constexpr (BANDS) {
-          px[u] = px[u] + (xr * xr + xi * xi);  // X += |rfft(x_c * win)|**2
-          py[u] = py[u] + (yr * yr + yi * yi);
-        }
+    owned_bins<M>(A.n_bins, [&](int u, int k) {
+      const BinPair z = split_pair(buf, k, n);
+      if constexpr (ROWS) {
+        ax[u] = ax[u] + hypotf(z.a.x, z.a.y);  // X += |rfft(x_c * win)|
+        ay[u] = ay[u] + hypotf(z.b.x, z.b.y);
       }
-    }
+      if constexpr (BANDS) {
+        px[u] = px[u] + power(z.a);  // X += |rfft(x_c * win)|**2
+        py[u] = py[u] + power(z.b);
+      }
+    });
     __syncthreads();  // buf reused by the next channel
   }
   float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // anchor, (x, lo), (x, hi), (y, lo), (y, hi)
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) {
-    const int k = threadIdx.x + u * kT;
-    if (k < A.n_bins) {
-      if constexpr (ROWS) {
-        float X = (CH == 1) ? ax[u] : ax[u] * 0.5f;  // X /= ch
-        const float Y = (CH == 1) ? ay[u] : ay[u] * 0.5f;
-        X = fmaxf(X, 1e-10f);                        // np.maximum(X, 1e-10)
-        ax[u] = Y / X;
-        if (k >= V.a0 && k < V.a1) acc[0] = acc[0] + ax[u];
-      }
-      if constexpr (BANDS) {
-        const float PX = (CH == 1) ? px[u] : px[u] * 0.5f;
-        const float PY = (CH == 1) ? py[u] : py[u] * 0.5f;
-        if (k >= A.band[0] && k < A.band[1]) {
-          acc[1] = acc[1] + PX;
-          acc[3] = acc[3] + PY;
-        }
-        if (k >= A.band[2] && k < A.band[3]) {
-          acc[2] = acc[2] + PX;
-          acc[4] = acc[4] + PY;
-        }
+  owned_bins<M>(A.n_bins, [&](int u, int k) {
+    if constexpr (ROWS) {
+      float X = (CH == 1) ? ax[u] : ax[u] * 0.5f;  // X /= ch
+      const float Y = (CH == 1) ? ay[u] : ay[u] * 0.5f;
+      X = fmaxf(X, 1e-10f);                        // np.maximum(X, 1e-10)
+      ax[u] = Y / X;
+      if constexpr (ANCHOR) {
+        if (in_range(k, V.a0, V.a1)) acc[0] = acc[0] + ax[u];
       }
     }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    float v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[w][j] = v;
-  }
-  __syncthreads();
+    if constexpr (BANDS) {
+      const float PX = (CH == 1) ? px[u] : px[u] * 0.5f;
+      const float PY = (CH == 1) ? py[u] : py[u] * 0.5f;
+      if (in_range(k, A.band[0], A.band[1])) {
+        acc[1] = acc[1] + PX;
+        acc[3] = acc[3] + PY;
+      }
+      if (in_range(k, A.band[2], A.band[3])) {
+        acc[2] = acc[2] + PX;
+        acc[4] = acc[4] + PY;
+      }
+    }
+  });
+  if constexpr (ANCHOR || BANDS) block_sums(acc, red);
   if constexpr (BANDS) {
-    if (threadIdx.x < 4) {
-      const int j = 1 + threadIdx.x;
-      float v = 0.f;
-      for (int i = 0; i < kT / 64; ++i) v += red[i][j];
-      V.bands[(int64_t)f * 4 + threadIdx.x] = v;
-    }
+    if (threadIdx.x < 4) V.bands[(int64_t)f * 4 + threadIdx.x] = wave_total(red, 1 + threadIdx.x);
   }
   if constexpr (ROWS) {
-    float s = 0.f;
-    for (int i = 0; i < kT / 64; ++i) s += red[i][0];
-    const int na = V.a1 - V.a0;
-    const float g = na > 0 ? s / (float)na : 0.f;
-    const bool scale = na > 0 && g > 0.f;  // anchor_gain > 0 (NaN: false)
+    float g = 0.f;
+    if constexpr (ANCHOR) g = wave_total(red, 0) / (float)(V.a1 - V.a0);
+    const bool scale = ANCHOR && g > 0.f;  // anchor_gain > 0 (NaN: false)
     float* o = A.out + (int64_t)f * A.n_bins;
-#pragma unroll
-    for (int u = 0; u < kMaxUB; ++u) {
-      const int k = threadIdx.x + u * kT;
-      if (k < A.n_bins) o[k] = scale ? ax[u] / g : ax[u];
-    }
+    owned_bins<M>(A.n_bins, [&](int u, int k) { o[k] = scale ? ax[u] / g : ax[u]; });
   }
 }
 
@@ -822,73 +786,43 @@ __global__ __launch_bounds__(kT) void k_an_verify(VerArgs V) {
 // verify_tilt_amplitude.py:74-92): per frame and bin
 //   d[k] = 20 log10(|B_k| + EPS) - 20 log10(|A_k| + EPS),   float32,
 // A = rfft(win * power_mono(x)), B = rfft(win * power_mono(y)).  Both spectra
-// come from one transform of a + ib split as in k_an_verify, the magnitudes are
-// hypotf as TOMATIS_AN_MAG's.  The two real bins are taken from float64 sums
-// formed while the frame is staged, for k_an_spec_mean's reason: both signals
-// are power monos, so bin n / 2 lies far under bin 0 and the logarithm would
-// turn the transform's rounding there into decibels.
+// come from one transform of a + ib, the magnitudes are hypotf as
+// TOMATIS_AN_MAG's; both signals are power monos, so the two real bins are
+// stage_pair's float64 sums.
 //
 // pair_diff stages frame f, transforms, splits and hands every bin the thread
-// owns (t, t + kT, ...: ascending) to use(u, k, d).  It leaves buf and red in
-// use: a caller that stages another frame puts a barrier in between.
+// owns to use(u, k, d).  It leaves buf and red in use: a caller that stages
+// another frame puts a barrier in between.
 // ---------------------------------------------------------------------------
 template <int M, bool BLUE, typename U>
 __device__ __forceinline__ void pair_diff(const SpecArgs& A, int f, float2* buf,
                                           double (*red)[4], U&& use) {
-  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;  // bins per thread (n/2+1 <= M/2+1)
   const int n = BLUE ? A.n_fft : M;  // constant for powers of two
   const int64_t p0 = (int64_t)f * A.hop;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double re[4] = {0.0, 0.0, 0.0, 0.0};  // (a, bin 0), (a, n/2), (b, 0), (b, n/2)
-  for (int i = threadIdx.x; i < n; i += kT) {
-    const float w = A.win[i];
-    const float a = power_mono(A.x, p0 + i, 1.0f) * w;
-    const float b = power_mono(A.y, p0 + i, 1.0f) * w;
-    buf[i] = make_float2(a, b);
-    re[0] += (double)a;
-    re[1] += (i & 1) ? -(double)a : (double)a;
-    re[2] += (double)b;
-    re[3] += (i & 1) ? -(double)b : (double)b;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double v = re[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wv][j] = v;
-  }
-  __syncthreads();
+  stage_pair<true>(
+      buf, red, n, A.win, [&](int i) { return power_mono(A.x, p0 + i, 1.0f); },
+      [&](int i) { return power_mono(A.y, p0 + i, 1.0f); });
   lds_dft<M, BLUE>(buf, n, A.tw, A.bb, A.bh);
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) {
-    const int k = threadIdx.x + u * kT;
-    if (k < A.n_bins) {
-      float ma, mb;
-      if (k == 0 || 2 * k == n) {  // the real bins: the float64 sums, rounded once
-        const int j = k == 0 ? 0 : 1;
-        double va = 0.0, vb = 0.0;
-        for (int i = 0; i < kT / 64; ++i) {
-          va += red[i][j];
-          vb += red[i][2 + j];
-        }
-        ma = fabsf((float)va);
-        mb = fabsf((float)vb);
-      } else {
-        const float2 zk = buf[k], zm = buf[mirror(k, n)];
-        ma = hypotf(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        mb = hypotf(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-      }
-      use(u, k, 20.0f * log10f(mb + kEps) - 20.0f * log10f(ma + kEps));
+  owned_bins<M>(A.n_bins, [&](int u, int k) {
+    float ma, mb;
+    if (const int j = real_bin(k, n); j >= 0) {
+      const float2 r = real_bins(red, j);
+      ma = fabsf(r.x);
+      mb = fabsf(r.y);
+    } else {
+      const BinPair z = split_pair(buf, k, n);
+      ma = hypotf(z.a.x, z.a.y);
+      mb = hypotf(z.b.x, z.b.y);
     }
-  }
+    use(u, k, 20.0f * log10f(mb + kEps) - 20.0f * log10f(ma + kEps));
+  });
 }
 
 // compute_tilt_index's two band means of d (reverse_engineer_params.py:62-76),
 // one workgroup per frame: means[f] = (mean d[lo0:lo1], mean d[hi0:hi1]) as
-// float64, each a float64 sum of the float32 values in a fixed order (a
-// thread's bins ascending, a shuffle tree, the four waves in order: no atomics)
-// over the bin count; an empty range gives 0 / 0 = NaN, numpy's mean of an
-// empty slice.  The row is stored where rows is given; the sums do not depend
-// on it.
+// float64, each a float64 block_sums of the float32 values over the bin count;
+// an empty range gives 0 / 0 = NaN, numpy's mean of an empty slice.  The row is
+// stored where rows is given; the sums do not depend on it.
 struct TiltArgs {
   SpecArgs S;     // out = rows [F][n_bins] or null, band = lo0, lo1, hi0, hi1
   double* means;  // [F][2]
@@ -905,31 +839,21 @@ __global__ __launch_bounds__(kT) void k_an_pair_tilt(TiltArgs T) {
   double acc[2] = {0.0, 0.0};
   pair_diff<M, BLUE>(A, f, buf, red, [&](int, int k, float d) {
     if (o) o[k] = d;
-    if (k >= A.band[0] && k < A.band[1]) acc[0] += (double)d;
-    if (k >= A.band[2] && k < A.band[3]) acc[1] += (double)d;
+    if (in_range(k, A.band[0], A.band[1])) acc[0] += (double)d;
+    if (in_range(k, A.band[2], A.band[3])) acc[1] += (double)d;
   });
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    double v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) sums[wv][j] = v;
-  }
-  __syncthreads();
+  block_sums(acc, sums);
   if (threadIdx.x < 2) {
     const int j = threadIdx.x;
-    double v = 0.0;
-    for (int i = 0; i < kT / 64; ++i) v += sums[i][j];
-    T.means[(int64_t)f * 2 + j] = v / (double)(A.band[2 * j + 1] - A.band[2 * j]);
+    T.means[(int64_t)f * 2 + j] =
+        wave_total(sums, j) / (double)(A.band[2 * j + 1] - A.band[2 * j]);
   }
 }
 
 // np.mean(diffs, axis=0) over a list of frames (verify_tilt_amplitude.py:98-99),
-// in float64 and in k_an_spec_mean's order: a workgroup owns kSlabFrames
-// consecutive list entries (a constant of the source) and walks them in order,
-// one float64 accumulator per owned bin in registers; the slab's sums go to
-// work[slab][bin] and k_an_spec_mean_fold adds the slabs in ascending order and
-// divides by the list's length.  frames == null: the list is 0, 1, 2, ...
+// in float64: slab_sums over kSlabFrames consecutive list entries, then
+// k_an_spec_mean_fold divides by the list's length.  frames == null: the list
+// is 0, 1, 2, ...
 constexpr int kSlabFrames = 16;
 
 struct DiffMeanArgs {
@@ -944,24 +868,12 @@ __global__ __launch_bounds__(kT) void k_an_pair_diff_mean(DiffMeanArgs D) {
   __shared__ float2 buf[M];
   __shared__ double red[kT / 64][4];
   const SpecArgs& A = D.S;
-  constexpr int kMaxUB = (M / 2 + 1 + kT - 1) / kT;
-  const int e0 = blockIdx.x * kSlabFrames;
-  const int e1 = min(e0 + kSlabFrames, D.n_sel);
-  double acc[kMaxUB];
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) acc[u] = 0.0;
-  for (int e = e0; e < e1; ++e) {
+  slab_sums<M>(kSlabFrames, D.n_sel, A.n_bins, D.work, [&](int e, auto& acc) {
     const int f = D.frames ? D.frames[e] : e;
     pair_diff<M, BLUE>(A, f, buf, red, [&](int u, int, float d) { acc[u] += (double)d; });
-    __syncthreads();  // buf and red are written again for the next frame
-  }
-  double* o = D.work + (int64_t)blockIdx.x * A.n_bins;
-#pragma unroll
-  for (int u = 0; u < kMaxUB; ++u) {
-    const int k = threadIdx.x + u * kT;
-    if (k < A.n_bins) o[k] = acc[u];
-  }
+  });
 }
+
 
 __global__ void k_an_fill_f64(double* __restrict__ out, int n, double v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1141,8 +1053,30 @@ __global__ void k_an_med_final(const MedState* __restrict__ st, int n_bins, int 
   out[b] = ((0.f + v1) + v2) / 2.0f;
 }
 
-// SpecArgs' FFT tables for n_fft: M, twiddles of M, Bluestein tables
-int dft_args(int n_fft, hipStream_t s, SpecArgs* A) {
+// F = the frames that lie inside n samples, 0 where there is none (the caller
+// then has nothing to do and returns TOMATIS_OK)
+int frame_count(int64_t n, int n_fft, int hop, int* F) {
+  *F = 0;
+  if (n < n_fft) return TOMATIS_OK;
+  const int64_t f = 1 + (n - n_fft) / hop;
+  if (f > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  *F = (int)f;
+  return TOMATIS_OK;
+}
+
+bool range_ok(int nb, int lo, int hi) { return lo >= 0 && hi >= lo && hi <= nb; }
+bool bands_ok(int nb, int lo0, int lo1, int hi0, int hi1) {
+  return range_ok(nb, lo0, lo1) && range_ok(nb, hi0, hi1);
+}
+
+// Completes a SpecArgs whose signals, window, output, scale and bands the caller
+// has set by name: the framing, M, the twiddles of M and, for a length that is
+// no power of two, the Bluestein tables.
+int spec_args(int n_fft, int hop, int F, hipStream_t s, SpecArgs* A) {
+  A->n_fft = n_fft;
+  A->hop = hop;
+  A->n_frames = F;
+  A->n_bins = n_fft / 2 + 1;
   A->M = dft_m(n_fft);
   if (A->M == 0) return TOMATIS_E_UNSUPPORTED;
   int rc = twiddles(A->M, s, &A->tw);
@@ -1153,6 +1087,14 @@ int dft_args(int n_fft, hipStream_t s, SpecArgs* A) {
   A->bh = c.h;
   return TOMATIS_OK;
 }
+
+void set_bands(SpecArgs* A, int lo0, int lo1, int hi0, int hi1) {
+  A->band[0] = lo0;
+  A->band[1] = lo1;
+  A->band[2] = hi0;
+  A->band[3] = hi1;
+}
+
 
 // calls f(integral_constant<M>, bool_constant<BLUE>) for the args' FFT size
 // (M = 16 .. 16384; Bluestein sizes start at M = 32 since n_fft >= 16)
@@ -1187,6 +1129,73 @@ int dispatch_m(const SpecArgs& A, L&& f) {
   return an_launch();
 }
 
+template <int V>
+constexpr std::integral_constant<int, V> ic{};
+
+// calls f(integral_constant<MODE>, integral_constant<CH>) for a validated level
+// mode and channel count (k_an_frame_r and k_an_frame_r_pw)
+template <typename L>
+void dispatch_level(int level_mode, int ch, L&& f) {
+  if (level_mode == TOMATIS_AN_LEVEL_POWER_MONO) f(ic<TOMATIS_AN_LEVEL_POWER_MONO>, ic<2>);
+  else if (ch == 1) f(ic<TOMATIS_AN_LEVEL_CHMEAN>, ic<1>);
+  else f(ic<TOMATIS_AN_LEVEL_CHMEAN>, ic<2>);
+}
+
+// calls f(integral_constant<CH>, ROWS, BANDS, ANCHOR as bool_constants) for
+// k_an_verify: rows without an anchor, anchored rows, bands, or anchored rows
+// and bands
+template <int CH, typename L>
+void verify_variant(bool rows, bool bands, bool anchor, L& f) {
+  constexpr std::true_type T{};
+  constexpr std::false_type N{};
+  if (!bands) anchor ? f(ic<CH>, T, N, T) : f(ic<CH>, T, N, N);
+  else if (!rows) f(ic<CH>, N, T, N);
+  else f(ic<CH>, T, T, T);
+}
+template <typename L>
+void dispatch_verify(int ch, bool rows, bool bands, bool anchor, L&& f) {
+  if (ch == 1) verify_variant<1>(rows, bands, anchor, f);
+  else verify_variant<2>(rows, bands, anchor, f);
+}
+
+// one launch of k_an_verify over F frames of the pair (V.S.x, V.S.y): the rows
+// where V.S.out is given, the bands where V.bands is; an empty anchor leaves the
+// rows as they are (TOMATIS_AN_RATIO)
+int launch_verify(VerArgs& V, int ch, int n_fft, int hop, int F, hipStream_t s) {
+  const int rc = spec_args(n_fft, hop, F, s, &V.S);
+  if (rc != TOMATIS_OK) return rc;
+  return dispatch_m(V.S, [&](auto m, auto b) {
+    dispatch_verify(ch, V.S.out != nullptr, V.bands != nullptr, V.a1 > V.a0, [&](auto c, auto r, auto bd, auto an) {
+      hipLaunchKernelGGL((k_an_verify<decltype(c)::value, decltype(m)::value, decltype(b)::value,
+                                      decltype(r)::value, decltype(bd)::value,
+                                      decltype(an)::value>),
+                         dim3((unsigned)F), dim3(kT), 0, s, V);
+    });
+  });
+}
+
+// the checks of the three pair entry points
+int an_verify(const float* x, const float* y, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
+              int32_t a0, int32_t a1, int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1,
+              const float* win, float* rows, float* bands, void* hs) {
+  if (!x || !y || !win || (!rows && !bands) || hop < 1 || ch < 1 || n_fft < 1 || n < 0)
+    return TOMATIS_E_ARG;
+  if (ch != 1 && ch != 2) return TOMATIS_E_UNSUPPORTED;
+  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
+  const int nb = n_fft / 2 + 1;
+  if (!range_ok(nb, a0, a1) || !bands_ok(nb, lo0, lo1, hi0, hi1)) return TOMATIS_E_ARG;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
+  VerArgs V{{}, bands, a0, a1};
+  V.S.x = x;
+  V.S.y = y;
+  V.S.win = win;
+  V.S.out = rows;
+  set_bands(&V.S, lo0, lo1, hi0, hi1);
+  return launch_verify(V, ch, n_fft, hop, F, (hipStream_t)hs);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1202,51 +1211,39 @@ int tomatis_an_frame_r(const float* x, int64_t n, int32_t ch, int32_t n_fft, int
   } else {
     return TOMATIS_E_ARG;
   }
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   hipStream_t s = (hipStream_t)hs;
-  const bool pm = level_mode == TOMATIS_AN_LEVEL_POWER_MONO;
   if (is_pow2(n_fft) && n_fft >= 256 && n_fft <= kMaxTreeN) {
-    // perfect tree over 128-sample leaves
-    const dim3 g((unsigned)((F + 3) / 4));
-    if (pm)
-      hipLaunchKernelGGL((k_an_frame_r<TOMATIS_AN_LEVEL_POWER_MONO, 2>), g, dim3(256), 0, s, x,
-                         n_fft, hop, (int)F, scale, r_out);
-    else if (ch == 1)
-      hipLaunchKernelGGL((k_an_frame_r<TOMATIS_AN_LEVEL_CHMEAN, 1>), g, dim3(256), 0, s, x,
-                         n_fft, hop, (int)F, scale, r_out);
-    else
-      hipLaunchKernelGGL((k_an_frame_r<TOMATIS_AN_LEVEL_CHMEAN, 2>), g, dim3(256), 0, s, x,
-                         n_fft, hop, (int)F, scale, r_out);
+    // perfect tree over 128-sample leaves, four frames per workgroup
+    dispatch_level(level_mode, ch, [&](auto mode, auto c) {
+      hipLaunchKernelGGL((k_an_frame_r<decltype(mode)::value, decltype(c)::value>),
+                         dim3((unsigned)((F + 3LL) / 4)), dim3(256), 0, s, x, n_fft, hop, F, scale,
+                         r_out);
+    });
     return an_launch();
   }
   PwProg q;
-  int rc = pw_program(n_fft, &q);
-  if (rc != TOMATIS_OK) return rc;
-  const dim3 g((unsigned)F);
-  if (pm)
-    hipLaunchKernelGGL((k_an_frame_r_pw<TOMATIS_AN_LEVEL_POWER_MONO, 2>), g, dim3(256), 0, s, x,
-                       n_fft, hop, scale, q.leaf, q.n_leaf, q.prog, q.n_prog, r_out);
-  else if (ch == 1)
-    hipLaunchKernelGGL((k_an_frame_r_pw<TOMATIS_AN_LEVEL_CHMEAN, 1>), g, dim3(256), 0, s, x,
-                       n_fft, hop, scale, q.leaf, q.n_leaf, q.prog, q.n_prog, r_out);
-  else
-    hipLaunchKernelGGL((k_an_frame_r_pw<TOMATIS_AN_LEVEL_CHMEAN, 2>), g, dim3(256), 0, s, x,
-                       n_fft, hop, scale, q.leaf, q.n_leaf, q.prog, q.n_prog, r_out);
+  if ((rc = pw_program(n_fft, &q)) != TOMATIS_OK) return rc;
+  dispatch_level(level_mode, ch, [&](auto mode, auto c) {
+    hipLaunchKernelGGL((k_an_frame_r_pw<decltype(mode)::value, decltype(c)::value>),
+                       dim3((unsigned)F), dim3(256), 0, s, x, n_fft, hop, scale, q.leaf, q.n_leaf,
+                       q.prog, q.n_prog, r_out);
+  });
   return an_launch();
 }
+
 
 int tomatis_an_frame_power_mean(const float* x, int64_t n, int32_t win, int32_t hop, float* out,
                                 void* hs) {
   if (!x || !out || n < 0 || win < 1 || hop < 1) return TOMATIS_E_ARG;
   if (win > kMaxMeanWin) return TOMATIS_E_UNSUPPORTED;
-  if (n < win) return TOMATIS_OK;
-  const int64_t F = 1 + (n - win) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  int F;
+  int rc = frame_count(n, win, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   PwProg q;
-  const int rc = pw_program(win, &q);
-  if (rc != TOMATIS_OK) return rc;
+  if ((rc = pw_program(win, &q)) != TOMATIS_OK) return rc;
   hipLaunchKernelGGL((k_an_frame_r_pw<kLevelPowerMean, 2>), dim3((unsigned)F), dim3(256), 0,
                      (hipStream_t)hs, x, win, hop, 1.0f, q.leaf, q.n_leaf, q.prog, q.n_prog, out);
   return an_launch();
@@ -1288,24 +1285,22 @@ int tomatis_an_spectra(const float* x, const float* y, int64_t n, int32_t ch, in
   } else {
     return TOMATIS_E_ARG;
   }
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   hipStream_t s = (hipStream_t)hs;
-  SpecArgs A{x, y, win, nullptr, nullptr, nullptr, out, n_fft, 0, hop, (int)F, n_fft / 2 + 1,
-             scale};
-  int rc = dft_args(n_fft, s, &A);
-  if (rc != TOMATIS_OK) return rc;
-  if (kind == TOMATIS_AN_RATIO) {
-    const dim3 g((unsigned)F);
-    return dispatch_m(A, [&](auto m, auto b) {
-      constexpr int MM = decltype(m)::value;
-      constexpr bool BL = decltype(b)::value;
-      if (ch == 1) hipLaunchKernelGGL((k_an_spec_ratio<1, MM, BL>), g, dim3(kT), 0, s, A);
-      else hipLaunchKernelGGL((k_an_spec_ratio<2, MM, BL>), g, dim3(kT), 0, s, A);
-    });
+  SpecArgs A;
+  A.x = x;
+  A.y = y;
+  A.win = win;
+  A.out = out;
+  A.sc = scale;
+  if (kind == TOMATIS_AN_RATIO) {  // the verify rows with an empty anchor (scale unused)
+    VerArgs V{A, nullptr, 0, 0};
+    return launch_verify(V, ch, n_fft, hop, F, s);
   }
-  const dim3 g((unsigned)((F + 1) / 2));
+  if ((rc = spec_args(n_fft, hop, F, s, &A)) != TOMATIS_OK) return rc;
+  const dim3 g((unsigned)((F + 1LL) / 2));
   const bool raw = sig_mode == TOMATIS_AN_SIG_RAW;
   return dispatch_m(A, [&](auto m, auto b) {
     constexpr int MM = decltype(m)::value;
@@ -1324,70 +1319,22 @@ int tomatis_an_band_energy(const float* x, int64_t n, int32_t n_fft, int32_t hop
                            const float* win, float* out, void* hs) {
   if (!x || !win || !out || hop < 1 || n_fft < 1) return TOMATIS_E_ARG;
   if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
-  const int nb = n_fft / 2 + 1;
-  if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  if (!bands_ok(n_fft / 2 + 1, lo0, lo1, hi0, hi1)) return TOMATIS_E_ARG;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   hipStream_t s = (hipStream_t)hs;
-  SpecArgs A{x, nullptr, win, nullptr, nullptr, nullptr, out, n_fft, 0, hop, (int)F, nb, 1.0f,
-             {lo0, lo1, hi0, hi1}};
-  int rc = dft_args(n_fft, s, &A);
-  if (rc != TOMATIS_OK) return rc;
-  const dim3 g((unsigned)((F + 1) / 2));
+  SpecArgs A;
+  A.x = x;
+  A.win = win;
+  A.out = out;
+  set_bands(&A, lo0, lo1, hi0, hi1);
+  if ((rc = spec_args(n_fft, hop, F, s, &A)) != TOMATIS_OK) return rc;
   return dispatch_m(A, [&](auto m, auto b) {
-    hipLaunchKernelGGL((k_an_band_pair<decltype(m)::value, decltype(b)::value>), g, dim3(kT), 0,
-                       s, A);
+    hipLaunchKernelGGL((k_an_band_pair<decltype(m)::value, decltype(b)::value>),
+                       dim3((unsigned)((F + 1LL) / 2)), dim3(kT), 0, s, A);
   });
 }
-
-}  // extern "C"
-
-namespace {
-
-// rows and / or bands of an input/output pair in one launch of k_an_verify
-int an_verify(const float* x, const float* y, int64_t n, int32_t ch, int32_t n_fft, int32_t hop,
-              int32_t a0, int32_t a1, int32_t lo0, int32_t lo1, int32_t hi0, int32_t hi1,
-              const float* win, float* rows, float* bands, void* hs) {
-  if (!x || !y || !win || (!rows && !bands) || hop < 1 || ch < 1 || n_fft < 1 || n < 0)
-    return TOMATIS_E_ARG;
-  if (ch != 1 && ch != 2) return TOMATIS_E_UNSUPPORTED;
-  if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
-  const int nb = n_fft / 2 + 1;
-  if (a0 < 0 || a1 < a0 || a1 > nb) return TOMATIS_E_ARG;
-  if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)hs;
-  VerArgs V{{x, y, win, nullptr, nullptr, nullptr, rows, n_fft, 0, hop, (int)F, nb, 1.0f,
-             {lo0, lo1, hi0, hi1}},
-            bands, a0, a1};
-  int rc = dft_args(n_fft, s, &V.S);
-  if (rc != TOMATIS_OK) return rc;
-  const dim3 g((unsigned)F);
-  const int mode = (rows ? 1 : 0) | (bands ? 2 : 0);
-  return dispatch_m(V.S, [&](auto m, auto b) {
-    constexpr int MM = decltype(m)::value;
-    constexpr bool BL = decltype(b)::value;
-#define TM_AN_VERIFY(CHN, R, B) \
-  hipLaunchKernelGGL((k_an_verify<CHN, MM, BL, R, B>), g, dim3(kT), 0, s, V)
-    if (ch == 1) {
-      if (mode == 1) TM_AN_VERIFY(1, true, false);
-      else if (mode == 2) TM_AN_VERIFY(1, false, true);
-      else TM_AN_VERIFY(1, true, true);
-    } else {
-      if (mode == 1) TM_AN_VERIFY(2, true, false);
-      else if (mode == 2) TM_AN_VERIFY(2, false, true);
-      else TM_AN_VERIFY(2, true, true);
-    }
-#undef TM_AN_VERIFY
-  });
-}
-
-}  // namespace
-
-extern "C" {
 
 int tomatis_an_anchored_ratio(const float* x, const float* y, int64_t n, int32_t ch,
                               int32_t n_fft, int32_t hop, int32_t a0, int32_t a1,
@@ -1439,17 +1386,17 @@ int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_ff
   } else {
     return TOMATIS_E_ARG;
   }
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   hipStream_t s = (hipStream_t)hs;
-  const int nb = n_fft / 2 + 1;
-  MeanArgs B{{x, nullptr, win, nullptr, nullptr, nullptr, nullptr, n_fft, 0, hop, (int)F, nb,
-              scale},
-             work};
-  int rc = dft_args(n_fft, s, &B.S);
-  if (rc != TOMATIS_OK) return rc;
-  const int slabs = (int)(((F + 1) / 2 + kSlabPairs - 1) / kSlabPairs);
+  MeanArgs B{{}, work};
+  B.S.x = x;
+  B.S.win = win;
+  B.S.sc = scale;
+  if ((rc = spec_args(n_fft, hop, F, s, &B.S)) != TOMATIS_OK) return rc;
+  const int nb = B.S.n_bins;
+  const int slabs = (int)(((F + 1LL) / 2 + kSlabPairs - 1) / kSlabPairs);
   const dim3 g((unsigned)slabs);
   const bool raw = sig_mode == TOMATIS_AN_SIG_RAW;
   rc = dispatch_m(B.S, [&](auto m, auto b) {
@@ -1463,7 +1410,7 @@ int tomatis_an_spectrum_mean(const float* x, int64_t n, int32_t ch, int32_t n_ff
   });
   if (rc != TOMATIS_OK) return rc;
   hipLaunchKernelGGL(k_an_spec_mean_fold, dim3((nb + 63) / 64), dim3(64), 0, s,
-                     (const double*)work, slabs, nb, (int)F, out);
+                     (const double*)work, slabs, nb, F, out);
   return an_launch();
 }
 
@@ -1472,21 +1419,21 @@ int tomatis_an_pair_tilt(const float* x, const float* y, int64_t n, int32_t n_ff
                          float* rows, double* band_means, void* hs) {
   if (!x || !y || !win || !band_means || hop < 1 || n_fft < 1 || n < 0) return TOMATIS_E_ARG;
   if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
-  const int nb = n_fft / 2 + 1;
-  if (lo0 < 0 || lo1 < lo0 || lo1 > nb || hi0 < 0 || hi1 < hi0 || hi1 > nb) return TOMATIS_E_ARG;
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  if (!bands_ok(n_fft / 2 + 1, lo0, lo1, hi0, hi1)) return TOMATIS_E_ARG;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   hipStream_t s = (hipStream_t)hs;
-  TiltArgs T{{x, y, win, nullptr, nullptr, nullptr, rows, n_fft, 0, hop, (int)F, nb, 1.0f,
-              {lo0, lo1, hi0, hi1}},
-             band_means};
-  int rc = dft_args(n_fft, s, &T.S);
-  if (rc != TOMATIS_OK) return rc;
-  const dim3 g((unsigned)F);
+  TiltArgs T{{}, band_means};
+  T.S.x = x;
+  T.S.y = y;
+  T.S.win = win;
+  T.S.out = rows;
+  set_bands(&T.S, lo0, lo1, hi0, hi1);
+  if ((rc = spec_args(n_fft, hop, F, s, &T.S)) != TOMATIS_OK) return rc;
   return dispatch_m(T.S, [&](auto m, auto b) {
-    hipLaunchKernelGGL((k_an_pair_tilt<decltype(m)::value, decltype(b)::value>), g, dim3(kT), 0,
-                       s, T);
+    hipLaunchKernelGGL((k_an_pair_tilt<decltype(m)::value, decltype(b)::value>),
+                       dim3((unsigned)F), dim3(kT), 0, s, T);
   });
 }
 
@@ -1503,9 +1450,9 @@ int tomatis_an_pair_diff_mean(const float* x, const float* y, int64_t n, int32_t
       n_sel < 0)
     return TOMATIS_E_ARG;
   if (dft_m(n_fft) == 0) return TOMATIS_E_UNSUPPORTED;
-  if (n < n_fft) return TOMATIS_OK;
-  const int64_t F = 1 + (n - n_fft) / hop;
-  if (F > INT32_MAX) return TOMATIS_E_UNSUPPORTED;
+  int F;
+  int rc = frame_count(n, n_fft, hop, &F);
+  if (rc != TOMATIS_OK || F == 0) return rc;
   if (!frames && n_sel != F) return TOMATIS_E_ARG;
   if (frames) {  // host memory: checked here, before anything is launched
     for (int32_t e = 0; e < n_sel; ++e)
@@ -1523,19 +1470,19 @@ int tomatis_an_pair_diff_mean(const float* x, const float* y, int64_t n, int32_t
   const int32_t* list = nullptr;
   if (frames) {
     int32_t* dl = reinterpret_cast<int32_t*>(work + (int64_t)slabs * nb);
-    const int rc = an_fail(hipMemcpyAsync(dl, frames, sizeof(int32_t) * (size_t)n_sel,
-                                          hipMemcpyHostToDevice, s));
+    rc = an_fail(hipMemcpyAsync(dl, frames, sizeof(int32_t) * (size_t)n_sel,
+                                hipMemcpyHostToDevice, s));
     if (rc != TOMATIS_OK) return rc;
     list = dl;
   }
-  DiffMeanArgs D{{x, y, win, nullptr, nullptr, nullptr, nullptr, n_fft, 0, hop, (int)F, nb, 1.0f},
-                 list, n_sel, work};
-  int rc = dft_args(n_fft, s, &D.S);
-  if (rc != TOMATIS_OK) return rc;
-  const dim3 g((unsigned)slabs);
+  DiffMeanArgs D{{}, list, n_sel, work};
+  D.S.x = x;
+  D.S.y = y;
+  D.S.win = win;
+  if ((rc = spec_args(n_fft, hop, F, s, &D.S)) != TOMATIS_OK) return rc;
   rc = dispatch_m(D.S, [&](auto m, auto b) {
-    hipLaunchKernelGGL((k_an_pair_diff_mean<decltype(m)::value, decltype(b)::value>), g,
-                       dim3(kT), 0, s, D);
+    hipLaunchKernelGGL((k_an_pair_diff_mean<decltype(m)::value, decltype(b)::value>),
+                       dim3((unsigned)slabs), dim3(kT), 0, s, D);
   });
   if (rc != TOMATIS_OK) return rc;
   hipLaunchKernelGGL(k_an_spec_mean_fold, dim3((nb + 63) / 64), dim3(64), 0, s,
